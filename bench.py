@@ -6,6 +6,14 @@ Contract (driver): ``python bench.py --gpus N --steps K --warmup W``; for N > 1 
 EXACTLY K timed optimizer steps bracketed by barrier + device sync; the time is the MAX over ranks;
 rank 0 prints one JSON line. Every timed step is a full training step: forward, backward, gradient
 reduction, optimizer step on fp32 masters for every parameter -- no skipped work.
+A plain run does only that: set-up, warm-up, the timed steps, the result line (at N > 1 the first
+warm-up step also carries the collective fingerprint check every multi-rank run needs). ``--full``
+adds what else the benchmark measures in steps of its own: the torch.profiler attribution step of
+``SXE_BENCH_TORCH_PROFILE``.
+``--dump-outputs DIR`` writes what the last timed step handed its caller as ``DIR/<name>.npy``
+(float32): ``loss`` (one value per micro-step) and ``params`` (a fixed, seeded sample of every fp32
+master parameter after the step's update, concatenated in ``named_parameters`` order). Seeds are
+fixed, so equal arguments give equal inputs and two builds can be compared output for output.
 Data: synthetic token ids (uniform over the vocabulary); weights: random init of the named
 architecture (no network access for checkpoints/datasets).
 
@@ -214,6 +222,34 @@ def _attribute_step(train_step, out_dir):
             f.write(f"{ms:9.2f} ms {n:5d}x  {k}\n      ops: {chain}\n      at: {stack}\n")
 
 
+DUMP_PARAM_BYTES = 48 << 20  # float32 bytes of the parameter sample of --dump-outputs (64 MB in all)
+
+
+def _dump_outputs(out_dir, model, losses, write):
+    """--dump-outputs: the micro-step losses of the last timed step and a seeded sample of every
+    parameter's fp32 master after it (the full-parameter getter is a collective over the ZeRO
+    partition group, so every rank calls this; `write` is true on the rank that stores the files)."""
+    import numpy as np
+    from shuffle_exchange_amd.utils.tensor_fragment import safe_get_full_fp32_param
+    params = list(model.parameters())
+    per = max(1, DUMP_PARAM_BYTES // 4 // max(1, len(params)))
+    parts = []
+    with torch.no_grad():
+        for i, p in enumerate(params):
+            try:
+                full = safe_get_full_fp32_param(p).reshape(-1)
+            except ValueError:  # not under the ZeRO optimizer (frozen): the tensor itself
+                full = p.detach().float().reshape(-1)
+            if full.numel() > per:
+                g = torch.Generator().manual_seed(977 + i)
+                full = full[torch.randint(full.numel(), (per,), generator=g).to(full.device)]
+            parts.append(full.cpu())
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "loss.npy"), losses.detach().float().cpu().numpy())
+        np.save(os.path.join(out_dir, "params.npy"), torch.cat(parts).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -237,6 +273,12 @@ def main():
                          "host; default 1.0 = the whole optimizer, the reference's ZeRO-Infinity setting)")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu = plumbing dry-run over gloo (tests only; invalid for the metric)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline figure that take steps of their own: "
+                         "the SXE_BENCH_TORCH_PROFILE attribution step")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32): "
+                         "loss (per micro-step), params (seeded sample of the updated fp32 masters)")
     args = ap.parse_args()
     c = CONFIGS[args.config]
     on_gpu = args.device == "cuda"
@@ -324,8 +366,10 @@ def main():
     from shuffle_exchange_amd.parallel import groups
     sp_rank = groups.get_sequence_parallel_rank() if sp > 1 else 0
 
+    step_losses = [None] * gas  # the last step's micro-step losses (--dump-outputs)
+
     def train_step():
-        for _ in range(gas):
+        for k in range(gas):
             # a fresh synthetic batch every micro-step (generated on the device: no H2D in the loop)
             batch = torch.randint(0, cfg.vocab_size, (mbs, seq), generator=gen, device=dev)
             if sp > 1:
@@ -334,6 +378,7 @@ def main():
                 loss = engine(b["input_ids"], labels=b["labels"], position_ids=b["position_ids"], shift_labels=False)
             else:
                 loss = engine(batch, labels=batch)
+            step_losses[k] = loss.detach()
             engine.backward(loss)
             engine.step()
         return loss
@@ -374,7 +419,13 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     vol = dist.get_comm_volume()
-    prof_dir = os.environ.get("SXE_BENCH_TORCH_PROFILE")
+    peak_mem = torch.cuda.max_memory_allocated() if on_gpu else None
+    if args.dump_outputs:
+        losses = torch.stack([l.float().reshape(()) for l in step_losses])
+        if sp > 1:  # each SP rank holds its shard's share of the loss
+            dist.all_reduce(losses, group=groups.get_sequence_parallel_group())
+        _dump_outputs(args.dump_outputs, model, losses, rank == 0)
+    prof_dir = os.environ.get("SXE_BENCH_TORCH_PROFILE") if args.full else None
     if prof_dir and rank == 0 and on_gpu:  # one extra step AFTER the timed loop: kernel -> op -> Python stack
         _attribute_step(train_step, prof_dir)
     dist.barrier()
@@ -426,7 +477,7 @@ def main():
                        "zero_effective": effective_zero(engine.optimizer), "sequence_parallel_size": sp,
                        "expert_parallel_size": ep},
             "tflops_per_gpu": round(tflops, 1),
-            "peak_mem_gb": round(torch.cuda.max_memory_allocated() / 2**30, 1) if on_gpu else None,
+            "peak_mem_gb": round(peak_mem / 2**30, 1) if on_gpu else None,
             "final_loss": round(float(final_loss.item()), 4),
             "comm_measured": {op: {"calls_per_step": round(n / args.steps, 2), "bytes_per_step": b // args.steps}
                               for op, (n, b) in sorted(vol.items())},

@@ -136,6 +136,58 @@ def test_bench_configs_wide_cpu(tmp_path, config, world):
         assert meas[op]["bytes_per_step"] == b, (op, meas[op], b)
 
 
+def _bench_one_rank(tmp_path, device, *extra):
+    env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS="2")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--warmup", "1", "--model", "llama-tiny",
+           "--device", device, "--seq", "64", "--mbs", "2", "--gas", "2", *extra]
+    r = subprocess.run(cmd, cwd=tmp_path, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-4000:]
+    return json.loads(lines[0])
+
+
+def _check_dump(d, out, steps):
+    import numpy as np
+    assert sorted(os.listdir(d)) == ["loss.npy", "params.npy"]
+    loss, params = np.load(d / "loss.npy"), np.load(d / "params.npy")
+    assert loss.dtype == np.float32 and params.dtype == np.float32
+    assert loss.shape == (2,) and np.isfinite(loss).all() and np.isfinite(params).all()  # one per micro-step
+    assert abs(float(loss[-1]) - out["final_loss"]) < 1e-3  # the last timed step's, not a later one's
+    assert loss.nbytes + params.nbytes <= 64 * 2**20 and params.size > 1000
+    assert out["steps"] == steps and out["ms_per_step"] > 0
+    return loss, params
+
+
+def test_bench_dump_outputs_cpu(tmp_path):
+    """--dump-outputs: float32 .npy files of the last timed step (micro-step losses, sampled updated
+    parameters), identical for identical arguments, different after a different number of steps
+    (--steps sets the timed steps); --full is accepted and leaves the result line's meaning alone."""
+    import numpy as np
+    a = _bench_one_rank(tmp_path, "cpu", "--steps", "2", "--dump-outputs", str(tmp_path / "a"))
+    b = _bench_one_rank(tmp_path, "cpu", "--steps", "2", "--full", "--dump-outputs", str(tmp_path / "b"))
+    c = _bench_one_rank(tmp_path, "cpu", "--steps", "3", "--dump-outputs", str(tmp_path / "c"))
+    la, pa = _check_dump(tmp_path / "a", a, 2)
+    lb, pb = _check_dump(tmp_path / "b", b, 2)
+    lc, pc = _check_dump(tmp_path / "c", c, 3)
+    assert np.array_equal(la, lb) and np.array_equal(pa, pb)
+    assert pa.shape == pc.shape and not np.array_equal(pa, pc) and not np.array_equal(la, lc)
+    for k in ("metric", "unit", "higher_is_better", "dtype", "config"):
+        assert a[k] == b[k], k
+    assert "diagnostics" not in a
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_gpu(tmp_path):
+    """The same dump from the HIP path on the GPU (tiny Llama, one rank)."""
+    out = _bench_one_rank(tmp_path, "cuda", "--steps", "2", "--dump-outputs", str(tmp_path / "g"))
+    _check_dump(tmp_path / "g", out, 2)
+    assert out["peak_mem_gb"] is not None
+
+
 def test_auto_ac_policy_partial_mlp_layers():
     """288 GB: Llama-3-8B at 32k tokens on one GPU checkpoints the MLP of only part of the layers;
     from 2 GPUs (16k tokens each) nothing is recomputed."""

@@ -14,7 +14,7 @@ for rep in 1 2; do
     echo "defer=$d rep=$rep $(grep '^{' $O/mixtral_defer${d}_$rep.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d.get("tflops_per_gpu"), d.get("peak_mem_gb"))')"
   done
 done
-SXE_BENCH_TORCH_PROFILE=$O/mixtral_attrib timeout -k 10 300 python bench.py --config mixtral-ep --steps 2 --warmup 2 > $O/mixtral_attrib.log 2>&1 \
+SXE_BENCH_TORCH_PROFILE=$O/mixtral_attrib timeout -k 10 300 python bench.py --full --config mixtral-ep --steps 2 --warmup 2 > $O/mixtral_attrib.log 2>&1 \
     || { tail -30 $O/mixtral_attrib.log; exit 1; }
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/gpu_suite.log 2>&1 \
     || { tail -40 $O/gpu_suite.log; exit 1; }
