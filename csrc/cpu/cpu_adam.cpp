@@ -151,8 +151,17 @@ static void lion_tile(float* __restrict p, const float* __restrict g, float* __r
   }
 }
 
+// Lion / Adagrad take (p, g, one state): host fp32 contiguous tensors of one size, as adam_step_ asks
+static void check_flat3(const char* op, const at::Tensor& p, const at::Tensor& g, const at::Tensor& s) {
+  TORCH_CHECK(p.device().is_cpu() && g.device().is_cpu() && s.device().is_cpu(), op, ": host tensors");
+  TORCH_CHECK(p.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat, op, ": fp32 master/state");
+  TORCH_CHECK(g.scalar_type() == at::kFloat, op, ": fp32 grads");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && s.is_contiguous(), op, ": contiguous");
+  TORCH_CHECK(g.numel() == p.numel() && s.numel() == p.numel(), op, ": size mismatch");
+}
+
 void lion_step_(at::Tensor p, at::Tensor g, at::Tensor m, double lr, double beta1, double beta2, double wd) {
-  TORCH_CHECK(g.scalar_type() == at::kFloat, "cpu_lion: fp32 grads");
+  check_flat3("cpu_lion", p, g, m);
   const int64_t n = p.numel(), T = 4096, tiles = (n + T - 1) / T;
   float *pp = p.data_ptr<float>(), *mp = m.data_ptr<float>();
   const float* gp = g.data_ptr<float>();
@@ -176,7 +185,7 @@ static void adagrad_tile(float* __restrict p, const float* __restrict g, float* 
 }
 
 void adagrad_step_(at::Tensor p, at::Tensor g, at::Tensor s, double lr, double eps, double wd) {
-  TORCH_CHECK(g.scalar_type() == at::kFloat, "cpu_adagrad: fp32 grads");
+  check_flat3("cpu_adagrad", p, g, s);
   const int64_t n = p.numel(), T = 4096, tiles = (n + T - 1) / T;
   float *pp = p.data_ptr<float>(), *sp = s.data_ptr<float>();
   const float* gp = g.data_ptr<float>();

@@ -206,7 +206,12 @@ void multi_tensor_adam_(at::TensorList p, at::TensorList g, at::TensorList m, at
     SXE_CHECK(p[i].scalar_type() == at::kFloat && p[i].is_contiguous() && g[i].is_contiguous() &&
                   m[i].is_contiguous() && v[i].is_contiguous(), "multi_tensor_adam_: fp32 contiguous");
     SXE_CHECK(dtype_of(g[i]) == gd, "multi_tensor_adam_: mixed grad dtypes");
+    SXE_CHECK(m[i].scalar_type() == at::kFloat && v[i].scalar_type() == at::kFloat, "multi_tensor_adam_: fp32 state");
     const int64_t n = p[i].numel();
+    SXE_CHECK(g[i].numel() == n && m[i].numel() == n && v[i].numel() == n, "multi_tensor_adam_: size mismatch in tensor ", i);
+    if (lp.size())
+      SXE_CHECK(dtype_of(lp[i]) == ld && lp[i].is_contiguous() && lp[i].numel() == n,
+                "multi_tensor_adam_: lp tensors must share one dtype, be contiguous and of p's size (tensor ", i, ")");
     for (int64_t s = 0; s < n; s += kChunk) {
       MTChunk c;
       c.p = p[i].data_ptr<float>() + s;
@@ -235,6 +240,22 @@ void multi_tensor_adam_(at::TensorList p, at::TensorList g, at::TensorList m, at
 }
 
 // ---------------------------------------------------------------------------------------------
+// Lion and Adagrad take (p, g, one fp32 state[, lp]) and index all of them with one element index:
+// fp32 master/state, every operand contiguous, of p's size and on p's device.
+static void check_flat3(const char* op, const at::Tensor& p, const at::Tensor& g, const at::Tensor& s,
+                        const at::Tensor* lp) {
+  SXE_CHECK(p.is_cuda() && g.device() == p.device() && s.device() == p.device(), op, ": operands on one GPU");
+  SXE_CHECK(p.scalar_type() == at::kFloat && s.scalar_type() == at::kFloat, op, ": fp32 master/state");
+  SXE_CHECK(p.is_contiguous() && g.is_contiguous() && s.is_contiguous(), op, ": contiguous");
+  SXE_CHECK(g.numel() == p.numel() && s.numel() == p.numel(), op, ": size mismatch");
+  if (lp) {
+    // a pinned host shard (ZeRO-3 offload_param with the optimizer in HBM) is written over the link
+    SXE_CHECK(lp->device() == p.device() || (lp->device().is_cpu() && lp->is_pinned()), op,
+              ": lp must be on p's device or in pinned host memory");
+    SXE_CHECK(lp->is_contiguous() && lp->numel() == p.numel(), op, ": lp must be contiguous and of p's size");
+  }
+}
+
 // Lion (reference deepspeed/ops/lion/fused_lion.py): u = sign(b1*m + (1-b1)*g); p -= lr*(u + wd*p);
 // m = b2*m + (1-b2)*g.
 template <DT G, DT L>
@@ -259,10 +280,10 @@ __global__ void __launch_bounds__(256) lion_flat_kernel(float* __restrict__ p, c
 void lion_flat_(at::Tensor p, at::Tensor g, at::Tensor m, c10::optional<at::Tensor> lp, c10::optional<at::Tensor> scale_t,
                 c10::optional<at::Tensor> skip_t, double lr, double beta1, double beta2, double weight_decay,
                 double grad_scale) {
-  SXE_CHECK(p.scalar_type() == at::kFloat && m.scalar_type() == at::kFloat, "lion_flat_: fp32 master/state");
+  const bool has_lp = lp.has_value() && lp->defined();
+  check_flat3("lion_flat_", p, g, m, has_lp ? &*lp : nullptr);
   const int64_t n = p.numel();
   if (n == 0) return;
-  const bool has_lp = lp.has_value() && lp->defined();
   c10::DeviceGuard guard(p.device());
   DT gd = dtype_of(g);
   DT ld = has_lp ? dtype_of(*lp) : DT::BF16;
@@ -298,9 +319,10 @@ __global__ void __launch_bounds__(256) adagrad_flat_kernel(float* __restrict__ p
 
 void adagrad_flat_(at::Tensor p, at::Tensor g, at::Tensor s, c10::optional<at::Tensor> lp, c10::optional<at::Tensor> scale_t,
                    c10::optional<at::Tensor> skip_t, double lr, double eps, double weight_decay, double grad_scale) {
+  const bool has_lp = lp.has_value() && lp->defined();
+  check_flat3("adagrad_flat_", p, g, s, has_lp ? &*lp : nullptr);
   const int64_t n = p.numel();
   if (n == 0) return;
-  const bool has_lp = lp.has_value() && lp->defined();
   c10::DeviceGuard guard(p.device());
   DT gd = dtype_of(g);
   DT ld = has_lp ? dtype_of(*lp) : DT::BF16;

@@ -39,15 +39,50 @@ def case_train(rank, world, ds_config, steps, mbs, seq, se_kwargs=None, seed=0):
     return {"params": full_params(eng), "losses": losses}
 
 
-def reference_train(ds_opt, steps, world, mbs, seq, seed=0, clip=0.0):
-    """Single-process reference on the global batch with torch.optim."""
+class _PlainLion(torch.optim.Optimizer):
+    """Lion from the formula in the header comment of csrc/kernels/optim.hip, in the parameters' own
+    dtype: u = sign(b1*m + (1-b1)*g); p -= lr*(u + wd*p); m = b2*m + (1-b2)*g."""
+
+    def __init__(self, params, lr=1e-4, betas=(0.9, 0.99), weight_decay=0.0):
+        super().__init__(params, dict(lr=lr, betas=betas, weight_decay=weight_decay))
+
+    @torch.no_grad()
+    def step(self):
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["exp_avg"] = torch.zeros_like(p)
+                m, g = st["exp_avg"], p.grad
+                u = (b1 * m + (1 - b1) * g).sign()
+                p.sub_(group["lr"] * (u + group["weight_decay"] * p))
+                m.mul_(b2).add_(g, alpha=1 - b2)
+
+
+def reference_train(ds_opt, steps, world, mbs, seq, seed=0, clip=0.0, dtype=None):
+    """Single-process reference on the global batch with torch.optim (Lion: _PlainLion). ``dtype``
+    (e.g. torch.float64) converts the model first, to measure what fp32 rounding alone moves."""
     model, cfg = tiny_llama(seed)
+    if dtype is not None:
+        model = model.to(dtype)
     p = ds_opt["params"]
-    if ds_opt["type"].lower() in ("adamw", "adam"):
+    kind = ds_opt["type"].lower()
+    if kind in ("adamw", "adam"):
         opt = torch.optim.AdamW(model.parameters(), lr=p["lr"], weight_decay=p.get("weight_decay", 0.0),
                                 betas=tuple(p.get("betas", (0.9, 0.999))), eps=p.get("eps", 1e-8))
-    else:
+    elif kind == "adagrad":
+        opt = torch.optim.Adagrad(model.parameters(), lr=p["lr"], eps=p.get("eps", 1e-10),
+                                  weight_decay=p.get("weight_decay", 0.0))
+    elif kind == "lion":
+        opt = _PlainLion(model.parameters(), lr=p["lr"], betas=tuple(p.get("betas", (0.9, 0.99))),
+                         weight_decay=p.get("weight_decay", 0.0))
+    elif kind == "sgd":
         opt = torch.optim.SGD(model.parameters(), lr=p["lr"])
+    else:
+        raise ValueError(f"reference_train: no reference optimizer for type {ds_opt['type']!r}")
     for b in global_batches(cfg, world, mbs, seq, steps):
         loss = model(b, labels=b)
         opt.zero_grad()
