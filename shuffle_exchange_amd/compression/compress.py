@@ -9,27 +9,124 @@ and channel pruning), ``BNLayer_Compress`` :611 (follows its conv's channel mask
 (``init_compression`` / ``redundancy_clean``, layer reduction from a teacher model),
 scheduler.py (``compression_scheduler`` turning techniques on at ``schedule_offset``).
 
-Fake quantization uses a straight-through estimator; masks are recomputed from the live weights
-at every enabled forward (magnitude criteria), and ``redundancy_clean`` bakes them in (and for row
-pruning physically shrinks the layer and the consumer's input columns).
+Fake quantization goes through ``ops.fake_quant`` (one fused HIP kernel on the GPU) under a
+straight-through estimator: the absmax / min-max grids down to 3 bits, the reference's ternary
+quantizer at 2 bits and its binary quantizer at 1 bit (compression/utils.py:148-222). Activation
+ranges are the batch's own ("dynamic") or a running range kept with momentum ("static", reference
+``QuantAct``). Masks are recomputed at every enabled forward, from the live weights (``method="l1"``,
+magnitude criteria) or for sparse pruning from trainable scores (``method="topk"``, reference
+``TopKBinarizer``), and ``redundancy_clean`` bakes them in (and for row pruning physically shrinks
+the layer and the consumer's input columns).
 """
+import math
 import re
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+_ACT_RANGE_MOMENTUM = 0.95  # reference QuantAct's act_range_momentum default
+
 
 class _STEQuant(torch.autograd.Function):
+    """Fake quantization (ops.fake_quant: the fused HIP kernel on the GPU) with a straight-through
+    backward."""
+
     @staticmethod
-    def forward(ctx, x, bits, groups, symmetric):
-        from ..runtime.quantize import fake_quantize
+    def forward(ctx, x, bits, groups, mode, value_range=None):
+        from ..ops.fake_quant import fake_quant
         g = groups if x.numel() % groups == 0 else 1
-        return fake_quantize(x, int(bits), g, symmetric)
+        return fake_quant(x, int(bits), g, mode, value_range)
 
     @staticmethod
     def backward(ctx, g):
-        return g, None, None, None
+        return g, None, None, None, None
+
+
+class TopKBinarizer(torch.autograd.Function):
+    """Mask of the ``ceil(ratio * numel)`` highest scores, with a straight-through gradient to the
+    scores (reference compression/utils.py:11)."""
+
+    @staticmethod
+    def forward(ctx, scores, ratio):
+        k = min(scores.numel(), max(0, math.ceil(ratio * scores.numel())))
+        mask = torch.zeros_like(scores).flatten()
+        mask[scores.detach().flatten().topk(k).indices] = 1
+        return mask.view_as(scores)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.clone(), None
+
+
+def _check_method(kind, method, topk=False):
+    if method == "l1" or (topk and method == "topk"):
+        return
+    if method == "topk":
+        raise ValueError(f"{kind} pruning: method 'topk' (learned scores) is implemented for sparse pruning only; "
+                         "use 'l1'")
+    raise ValueError(f"{kind} pruning: unknown method {method!r} (expected 'l1'" + (" or 'topk')" if topk else ")"))
+
+
+def _weight_mode(q):
+    """The quantizer for the current bit width: >= 3 bits the configured absmax / min-max grid,
+    2 bits ternary, 1 bit binary. The ramp ends at ``target_bits``, so at the target this is the
+    reference's rule (basic_layer.py enable_weight_quantization selects by ``target_bits``).
+    Deviation: the reference quantizes at ``target_bits`` from the first step, so its 1-bit target is
+    binary throughout; here the bit ramp this project adds runs first, and a ramp 8 -> 1 is
+    symmetric down to 3 bits, ternary at 2 and binary from 1 on. Widths >= 3 keep their results."""
+    if q["bits"] >= 3:
+        return "symmetric" if q["symmetric"] else "asymmetric"
+    return "ternary" if q["bits"] == 2 else "binary"
+
+
+def _quantize_weight(layer, w):
+    """Advance the layer's bit ramp (training only) and fake-quantize ``w`` at the current width."""
+    q = layer.wq
+    if layer.training:
+        q["step"] += 1
+        if q["bits"] > q["target"] and q["step"] % q["period"] == 0:
+            q["bits"] -= 1
+    return _STEQuant.apply(w, q["bits"], q["groups"], _weight_mode(q))
+
+
+def _prepare_sparse_scores(layer):
+    """The trainable scores of ``method="topk"`` sparse pruning, initialised as the reference does
+    (basic_layer.py:157-159). ``init_compression`` creates them, so an optimizer built right after
+    it trains them and a checkpoint loads strictly, whenever the scheduler turns the pruning on."""
+    if not hasattr(layer, "sparse_mask_scores"):
+        layer.sparse_mask_scores = nn.Parameter(torch.empty_like(layer.weight))
+        nn.init.kaiming_uniform_(layer.sparse_mask_scores, a=math.sqrt(5))
+
+
+def _prepare_static_range(layer):
+    """The running (min, max) buffer of ``range_calibration="static"``; zeros mean "not started"."""
+    if not hasattr(layer, "x_min_max"):
+        layer.register_buffer("x_min_max", torch.zeros(2, dtype=torch.float32, device=layer.weight.device))
+
+
+def _drop_scores(layer):
+    """After the topk mask is baked into the weight the learned scores have no further use."""
+    if hasattr(layer, "sparse_mask_scores"):
+        del layer.sparse_mask_scores
+        layer.sparse_method = "l1"
+
+
+def _quantize_input(layer, x):
+    """Activation fake quantization over the whole tensor: from the batch's own range ("dynamic") or
+    from the running range in the ``x_min_max`` buffer ("static", reference QuantAct
+    basic_layer.py:17), which training forwards update with momentum and no host sync."""
+    aq = layer.aq
+    mode = "symmetric" if aq["symmetric"] else "asymmetric"
+    if not aq.get("static"):
+        return _STEQuant.apply(x, aq["bits"], 1, mode)
+    r = layer.x_min_max
+    if layer.training:
+        with torch.no_grad():
+            cur = torch.stack(x.detach().aminmax()).to(r.dtype)
+            start = torch.where(r[0] == r[1], cur, r)  # first step: start from the batch range
+            r.copy_(start * _ACT_RANGE_MOMENTUM + cur * (1 - _ACT_RANGE_MOMENTUM))
+    return _STEQuant.apply(x, aq["bits"], 1, mode, r.float())
 
 
 class LinearLayer_Compress(nn.Linear):
@@ -59,28 +156,52 @@ class LinearLayer_Compress(nn.Linear):
     # -------------------------------------------------------------------------------- enabling
     def enable_weight_quantization(self, start_bits, target_bits, quantization_period, weight_quantization_enabled_in_forward=True,
                                    quantization_type="symmetric", num_groups=1):
+        if target_bits < 1:
+            raise ValueError(f"weight quantization: target_bits must be at least 1, got {target_bits}")
+        if target_bits <= 2 and quantization_type != "symmetric":
+            raise ValueError("weight quantization: only symmetric quantization is supported for "
+                             f"{'ternary (2-bit)' if target_bits == 2 else 'binary (1-bit)'} targets, "
+                             f"got {quantization_type!r}")
+        if start_bits <= 2 and quantization_type != "symmetric":
+            raise ValueError(f"weight quantization: start_bits {start_bits} selects the "
+                             f"{'ternary' if start_bits == 2 else 'binary'} quantizer, which is symmetric only, "
+                             f"got {quantization_type!r}")
+        if start_bits < 1:
+            raise ValueError(f"weight quantization: start_bits must be at least 1, got {start_bits}")
         self.wq = dict(bits=start_bits, target=target_bits, period=max(1, quantization_period), step=0,
                        symmetric=quantization_type == "symmetric", groups=num_groups)
         self.weight_quantization_enabled = True
 
     def enable_activation_quantization(self, bits, quantization_type="symmetric", range_calibration="dynamic"):
-        self.aq = dict(bits=bits, symmetric=quantization_type == "symmetric")
+        if range_calibration not in ("dynamic", "static"):
+            raise ValueError(f"activation quantization: unknown range_calibration {range_calibration!r} "
+                             "(expected 'dynamic' or 'static')")
+        self.aq = dict(bits=bits, symmetric=quantization_type == "symmetric", static=range_calibration == "static")
+        if self.aq["static"]:
+            _prepare_static_range(self)
         self.activation_quantization_enabled = True
 
     def enable_sparse_pruning(self, ratio, method="l1"):
+        _check_method("sparse", method, topk=True)
         self.sparse_ratio, self.sparse_method = ratio, method
+        if method == "topk":
+            _prepare_sparse_scores(self)
         self.sparse_pruning_enabled = True
 
     def enable_row_pruning(self, ratio, method="l1"):
+        _check_method("row", method)
         self.row_ratio = ratio
         self.row_pruning_enabled = True
 
     def enable_head_pruning(self, ratio, num_heads, method="l1"):
+        _check_method("head", method)
         self.head_ratio, self.num_heads = ratio, num_heads
         self.head_pruning_enabled = True
 
     # ------------------------------------------------------------------------------ masks
     def _sparse(self):
+        if self.sparse_method == "topk":  # learned scores; the gradient reaches them through w * mask
+            return TopKBinarizer.apply(self.sparse_mask_scores, self.sparse_ratio).to(self.weight.dtype)
         k = int(self.weight.numel() * self.sparse_ratio)
         thr = self.weight.detach().abs().flatten().kthvalue(max(1, self.weight.numel() - k)).values
         return (self.weight.detach().abs() > thr).to(self.weight.dtype)
@@ -114,17 +235,12 @@ class LinearLayer_Compress(nn.Linear):
             self.head_mask = self._heads()
             w = w * self.head_mask[None, :]
         if self.weight_quantization_enabled:
-            q = self.wq
-            if self.training:
-                q["step"] += 1
-                if q["bits"] > q["target"] and q["step"] % q["period"] == 0:
-                    q["bits"] -= 1
-            w = _STEQuant.apply(w, q["bits"], q["groups"], q["symmetric"])
+            w = _quantize_weight(self, w)
         return w
 
     def forward(self, x, skip_bias=False):
         if self.activation_quantization_enabled:
-            x = _STEQuant.apply(x, self.aq["bits"], 1, self.aq["symmetric"])
+            x = _quantize_input(self, x)
         b = None if skip_bias else self.bias
         if self.row_pruning_enabled and b is not None:
             b = b * self._rows()
@@ -137,6 +253,7 @@ class LinearLayer_Compress(nn.Linear):
         for a in ("sparse_pruning_enabled", "head_pruning_enabled", "weight_quantization_enabled",
                   "activation_quantization_enabled"):
             setattr(self, a, False)
+        _drop_scores(self)
 
 
 class Embedding_Compress(nn.Embedding):
@@ -160,12 +277,7 @@ class Embedding_Compress(nn.Embedding):
     def effective_weight(self):
         w = self.weight
         if self.weight_quantization_enabled:
-            q = self.wq
-            if self.training:
-                q["step"] += 1
-                if q["bits"] > q["target"] and q["step"] % q["period"] == 0:
-                    q["bits"] -= 1
-            w = _STEQuant.apply(w, q["bits"], q["groups"], q["symmetric"])
+            w = _quantize_weight(self, w)
         return w
 
     def forward(self, ids):
@@ -208,6 +320,7 @@ class Conv2dLayer_Compress(nn.Conv2d):
     _sparse = LinearLayer_Compress._sparse
 
     def enable_channel_pruning(self, ratio, method="l1"):
+        _check_method("channel", method)
         self.channel_ratio = ratio
         self.channel_pruning_enabled = True
 
@@ -228,17 +341,12 @@ class Conv2dLayer_Compress(nn.Conv2d):
             self.channel_mask = self._channels()
             w = w * self.channel_mask.view(-1, 1, 1, 1)
         if self.weight_quantization_enabled:
-            q = self.wq
-            if self.training:
-                q["step"] += 1
-                if q["bits"] > q["target"] and q["step"] % q["period"] == 0:
-                    q["bits"] -= 1
-            w = _STEQuant.apply(w, q["bits"], q["groups"], q["symmetric"])
+            w = _quantize_weight(self, w)
         return w
 
     def forward(self, x):
         if self.activation_quantization_enabled:
-            x = _STEQuant.apply(x, self.aq["bits"], 1, self.aq["symmetric"])
+            x = _quantize_input(self, x)
         b = self.bias
         if self.channel_pruning_enabled and b is not None:
             b = b * self._channels()
@@ -251,6 +359,7 @@ class Conv2dLayer_Compress(nn.Conv2d):
             self.bias.mul_(self._channels())
         for a in ("sparse_pruning_enabled", "weight_quantization_enabled", "activation_quantization_enabled"):
             setattr(self, a, False)
+        _drop_scores(self)
 
 
 class BNLayer_Compress(nn.BatchNorm2d):
@@ -324,8 +433,28 @@ def init_compression(model, deepspeed_config, teacher_model=None, mpu=None):
             elif (isinstance(child, nn.BatchNorm2d) and not isinstance(child, BNLayer_Compress)
                   and bn_wanted and _match(full, bn_wanted)):
                 setattr(mod, cname, BNLayer_Compress.from_bn(child))
+    _prepare_state(model, ct)
     model._sxe_compression_config = ct
     return model
+
+
+def _prepare_state(model, ct):
+    """Create, from the config, the parameters and buffers that techniques own (topk scores, static
+    activation ranges) on the layers they will apply to, as the reference's init_compression does.
+    The techniques themselves stay off until the scheduler reaches their ``schedule_offset``."""
+    for tech, key, value, attr, prepare in (
+            ("sparse_pruning", "method", "topk", "enable_sparse_pruning", _prepare_sparse_scores),
+            ("activation_quantization", "range_calibration", "static", "enable_activation_quantization",
+             _prepare_static_range)):
+        blk = ct.get(tech, {})
+        shared = blk.get("shared_parameters", {})
+        if not shared.get("enabled") or shared.get(key) != value:
+            continue
+        for _, _, mods, _ in _groups(blk):
+            pats = [m.replace("*", ".*") for m in mods]
+            for name, m in model.named_modules():
+                if _match(name, pats) and hasattr(m, attr):
+                    prepare(m)
 
 
 def _layer_reduction(model, lr, teacher=None):
@@ -382,12 +511,13 @@ class compression_scheduler:
             p.get("start_bits", 8), p.get("target_bits", 8), p.get("quantization_period", 1),
             quantization_type=s.get("quantization_type", "symmetric"), num_groups=s.get("quantize_groups", 1)))
         self._apply("activation_quantization", lambda m, s, p: m.enable_activation_quantization(
-            p.get("bits", 8), s.get("quantization_type", "symmetric")))
+            p.get("bits", 8), s.get("quantization_type", "symmetric"), s.get("range_calibration", "dynamic")))
         self._apply("sparse_pruning", lambda m, s, p: m.enable_sparse_pruning(p.get("dense_ratio", 0.5),
                                                                              s.get("method", "l1")))
-        self._apply("row_pruning", lambda m, s, p: m.enable_row_pruning(p.get("dense_ratio", 0.5)))
+        self._apply("row_pruning", lambda m, s, p: m.enable_row_pruning(p.get("dense_ratio", 0.5),
+                                                                          s.get("method", "l1")))
         self._apply("head_pruning", lambda m, s, p: m.enable_head_pruning(p.get("dense_ratio", 0.5),
-                                                                         s.get("num_heads", 1)))
+                                                                         s.get("num_heads", 1), s.get("method", "l1")))
         self._apply("channel_pruning", lambda m, s, p: m.enable_channel_pruning(p.get("dense_ratio", 0.5),
                                                                                s.get("method", "l1")))
 

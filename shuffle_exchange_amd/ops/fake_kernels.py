@@ -115,6 +115,11 @@ def _gather_rows(src, idx, offset=0, add=None):
     return src.new_empty((idx.numel(),) + tuple(src.shape[1:]))
 
 
+@_reg("sxe::fake_quant")
+def _fake_quant(x, groups, mode, bits, range=None):
+    return torch.empty_like(x)
+
+
 @_reg("sxe::scatter_rows_")
 def _scatter_rows(dst, idx, src):
     return None
