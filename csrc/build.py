@@ -69,23 +69,32 @@ def _compile(kind, src, obj, flags, force):
     return obj, True
 
 
-def build(jobs=None, force=False, only=None, verbose=True):
-    inc, lib, abi = _torch_paths()
+def _common_flags(csrc):
+    inc, _, abi = _torch_paths()
     py_inc = sysconfig.get_paths()["include"]
-    os.makedirs(BUILD_DIR, exist_ok=True)
     common = ["-O3", "-fPIC", "-std=c++17", f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
-              "-DTORCH_API_INCLUDE_EXTENSION_H", "-I" + os.path.join(CSRC, "include"), "-I" + py_inc]
-    common += ["-I" + p for p in inc]
-    hip_flags = common + [f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
-                          "-fno-gpu-rdc", "-munsafe-fp-atomics", "-Wno-unused-result",
-                          "-Wno-return-type", "-ffp-contract=fast"]
+              "-DTORCH_API_INCLUDE_EXTENSION_H", "-I" + os.path.join(csrc, "include"), "-I" + py_inc]
+    return common + ["-I" + p for p in inc]
+
+
+def hip_flags(csrc=CSRC):
+    """hipcc flags of every csrc/kernels/*.hip; `csrc` is the tree whose include/ is searched."""
+    return _common_flags(csrc) + [f"--offload-arch={ARCH}", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",
+                                  "-fno-gpu-rdc", "-munsafe-fp-atomics", "-Wno-unused-result",
+                                  "-Wno-return-type", "-ffp-contract=fast"]
+
+
+def build(jobs=None, force=False, only=None, verbose=True):
+    lib = _torch_paths()[1]
+    os.makedirs(BUILD_DIR, exist_ok=True)
     # -fno-math-errno: std::sqrt in the optimizer loops may not set errno, else GCC keeps them scalar
-    cpu_flags = common + ["-fopenmp", "-fno-math-errno", "-Wall", "-Wno-unused-function", "-Wno-sign-compare"]
+    cpu_flags = _common_flags(CSRC) + ["-fopenmp", "-fno-math-errno", "-Wall", "-Wno-unused-function",
+                                       "-Wno-sign-compare"]
     targets = []
     if only in (None, "hip"):
         hip_srcs = sorted(f for f in os.listdir(os.path.join(CSRC, "kernels")) if f.endswith(".hip"))
         targets.append(("hip", [os.path.join(CSRC, "kernels", f) for f in hip_srcs],
-                        os.path.join(OUT_DIR, "_sxe_hip.so"), hip_flags,
+                        os.path.join(OUT_DIR, "_sxe_hip.so"), hip_flags(),
                         ["-lc10", "-lc10_hip", "-ltorch", "-ltorch_cpu", "-ltorch_hip", "-lamdhip64"]))
     if only in (None, "cpu"):
         cpu_srcs = sorted(f for f in os.listdir(os.path.join(CSRC, "cpu")) if f.endswith(".cpp"))

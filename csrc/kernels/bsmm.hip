@@ -15,6 +15,7 @@
 // vector loads along the reduction dim when it is unit-stride, element gathers otherwise (the
 // transposed operand of a backward product); operands stay L2-resident across the tiles of a block.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 
 #include <torch/library.h>
 
@@ -22,7 +23,7 @@ namespace sxe {
 namespace bsm {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mf::bf16x8;
 
 template <DT T>
 __device__ __forceinline__ f32x4 mma(u16x8 a, u16x8 b, f32x4 c) {

@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(256, 2) fwd_kernel(Args a, unsigned short* __r
     for (int j = 0; j < 2; ++j) {
       s[j] = zero16();
 #pragma unroll
-      for (int t2 = 0; t2 < DH / 16; ++t2) s[j] = mfma(lds_row16(kt, 32 * j + r, 2 * t2 + hf), qf[t2], s[j]);
+      for (int t2 = 0; t2 < DH / 16; ++t2) s[j] = mfma(lds_row16<128>(kt, 32 * j + r, 2 * t2 + hf), qf[t2], s[j]);
     }
     float mx = -INFINITY;
 #pragma unroll
@@ -144,7 +144,7 @@ __global__ void __launch_bounds__(256, 2) fwd_kernel(Args a, unsigned short* __r
       for (int s2 = 0; s2 < 2; ++s2) {
         const bf16x8 pb = acc_to_b(s[j], s2);
 #pragma unroll
-        for (int dt = 0; dt < DH / 32; ++dt) oacc[dt] = mfma(lds_trA(vt, 32 * j + 16 * s2, dt, lane), pb, oacc[dt]);
+        for (int dt = 0; dt < DH / 32; ++dt) oacc[dt] = mfma(lds_trA<128>(vt, 32 * j + 16 * s2, dt, lane), pb, oacc[dt]);
       }
     if (more) {
       sk.store(smem + (cur ^ 1) * BUF);
@@ -222,8 +222,8 @@ __global__ void __launch_bounds__(256, 2) dq_kernel(Args a, unsigned short* __re
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int t2 = 0; t2 < DH / 16; ++t2) {
-        s = mfma(lds_row16(kt, 32 * j + r, 2 * t2 + hf), qf[t2], s);
-        dp = mfma(lds_row16(vt, 32 * j + r, 2 * t2 + hf), df[t2], dp);
+        s = mfma(lds_row16<128>(kt, 32 * j + r, 2 * t2 + hf), qf[t2], s);
+        dp = mfma(lds_row16<128>(vt, 32 * j + r, 2 * t2 + hf), df[t2], dp);
       }
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
@@ -236,7 +236,7 @@ __global__ void __launch_bounds__(256, 2) dq_kernel(Args a, unsigned short* __re
       for (int s2 = 0; s2 < 2; ++s2) {
         const bf16x8 db = acc_to_b(s, s2);
 #pragma unroll
-        for (int dt = 0; dt < DH / 32; ++dt) acc[dt] = mfma(lds_trA(kt, 32 * j + 16 * s2, dt, lane), db, acc[dt]);
+        for (int dt = 0; dt < DH / 32; ++dt) acc[dt] = mfma(lds_trA<128>(kt, 32 * j + 16 * s2, dt, lane), db, acc[dt]);
       }
     }
     if (more) {
@@ -328,8 +328,8 @@ __global__ void __launch_bounds__(256, 2) dkdv_kernel(Args a, unsigned short* __
     f32x16 s = zero16(), dp = zero16();
 #pragma unroll
     for (int t2 = 0; t2 < DH / 16; ++t2) {
-      s = mfma(lds_row16(qt, r, 2 * t2 + hf), kf[t2], s);    // S  [query][key]
-      dp = mfma(lds_row16(dt_, r, 2 * t2 + hf), vf[t2], dp);  // dP [query][key]
+      s = mfma(lds_row16<128>(qt, r, 2 * t2 + hf), kf[t2], s);    // S  [query][key]
+      dp = mfma(lds_row16<128>(dt_, r, 2 * t2 + hf), vf[t2], dp);  // dP [query][key]
     }
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -349,8 +349,8 @@ __global__ void __launch_bounds__(256, 2) dkdv_kernel(Args a, unsigned short* __
       const bf16x8 db = acc_to_b(dp, s2);
 #pragma unroll
       for (int t = 0; t < DH / 32; ++t) {
-        dva[t] = mfma(lds_trA(dt_, 16 * s2, t, lane), pb, dva[t]);  // dV^T += dO^T P
-        dka[t] = mfma(lds_trA(qt, 16 * s2, t, lane), db, dka[t]);   // dK^T += Q^T dS
+        dva[t] = mfma(lds_trA<128>(dt_, 16 * s2, t, lane), pb, dva[t]);  // dV^T += dO^T P
+        dka[t] = mfma(lds_trA<128>(qt, 16 * s2, t, lane), db, dka[t]);   // dK^T += Q^T dS
       }
     }
     if (more) store(smem + (cur ^ 1) * SLOT);

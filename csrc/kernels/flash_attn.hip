@@ -26,63 +26,20 @@
 //    atomics, deterministic.
 //  * heavy-first block order for the causal triangle.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 #include <type_traits>
 
 namespace sxe {
 namespace fa {
+using namespace mf;  // swizzled LDS image, transposed reads, MFMA helpers, LDS-DMA: see sxe_mfma.h
 
 constexpr int NW = 4;           // waves per workgroup
 constexpr int QW = 32;          // rows per wave
 constexpr int QB = NW * QW;     // 128 rows per workgroup
 constexpr int KT = 64;          // keys per K/V tile (forward / dQ)
-constexpr float LOG2E = 1.4426950408889634f;
-constexpr float LN2 = 0.6931471805599453f;
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// Byte offset of 16-byte chunk `ch` (0..D/8-1) of row `row` in a swizzled [rows][D bf16] tile: the
-// chunk index is XORed with a 4-bit function of the row (3 bits when a row has only 8 chunks) so
-// both the row reads (ds_read_b128) and the transposed 4-row reads (ds_read_b64_tr_b16) spread over
-// the banks (guide T10, image (b)); the XOR is an involution, which the direct-to-LDS loader uses.
-template <int D>
-__device__ __forceinline__ int soff(int row, int ch) {
-  constexpr int CH = D / 8;
-  const int f = (((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1);
-  return row * (2 * D) + 16 * (ch ^ f);
-}
-
-template <int D>
-__device__ __forceinline__ bf16x8 lds_row16(const char* base, int row, int ch) {
-  return *reinterpret_cast<const bf16x8*>(base + soff<D>(row, ch));
-}
-
-// Transposed read: 4 consecutive rows x one column per lane (ds_read_b64_tr_b16).
-__device__ __forceinline__ i16x4 lds_tr(const char* base, int byte_off) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) i16x4*)(const_cast<char*>(base) + byte_off));
-}
-
-// A operand of a 32x32x16 MFMA taken from a row-major [rows][d] LDS tile, transposed:
-// A[m = d][k] with d = 32*dt + (lane&31), k permuted to match an accumulator used as B operand:
-// element j of lane half h <- tile row (row0 + 8*(j>>2) + 4h + (j&3)), column d.
-template <int D>
-__device__ __forceinline__ bf16x8 lds_trA(const char* base, int row0, int dt, int lane) {
-  const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3, h = g >> 1;
-  const int ch = 4 * dt + 2 * (g & 1) + (p >> 1);
-  const int row = row0 + 4 * h + q;
-  i16x4 lo = lds_tr(base, soff<D>(row, ch) + 8 * (p & 1));
-  i16x4 hi = lds_tr(base, soff<D>(row + 8, ch) + 8 * (p & 1));
-  // whole-vector bitcast: element-wise bf16 inserts from the tr-read result miscompile (hipcc 7.2)
-  const i16x8 c = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, c);
-}
-
-// Per-lane byte offsets of the two LDS read forms above, computed once per kernel: the swizzle only
+// Per-lane byte offsets of mf::lds_row16 and mf::lds_trA, computed once per kernel: the swizzle only
 // looks at the low 4 row bits, so for a tile row base row0 that is a multiple of 16
 //   lds_row16(base, row0 + r, 2 t2 + h)  = base + 2D row0 + row[t2]
 //   lds_trA(base, row0, dt, lane)        = tr_read(base + 2D row0, tr[dt][0], tr[dt][1])
@@ -109,51 +66,18 @@ __device__ __forceinline__ bf16x8 lds_row_at(const char* base, int off) {
   return *reinterpret_cast<const bf16x8*>(base + off);
 }
 __device__ __forceinline__ bf16x8 lds_tr_at(const char* base, const int (&o)[2]) {
-  i16x4 lo = lds_tr(base, o[0]);
-  i16x4 hi = lds_tr(base, o[1]);
-  const i16x8 c = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, c);
+  return tr_pair(lds_tr(base, o[0]), lds_tr(base, o[1]));
 }
-
-// Accumulator registers 8s..8s+7 -> bf16 B operand (k-step s of the accumulator-as-operand trick).
-__device__ __forceinline__ bf16x8 acc_to_b(const f32x16& a, int s) {
-  bf16x8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (__bf16)a[8 * s + e];
-  return r;
-}
-
-// value of the lane 32 apart (lane ^ 32) via v_permlane32_swap: a VALU op instead of a
-// ds_bpermute round trip through the LDS
-__device__ __forceinline__ float xor32(float x) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-  return __uint_as_float((threadIdx.x & 32) ? r[0] : r[1]);
-}
-
-// raw v_exp_f32: exp2f() wraps it in denormal range reduction, pure VALU overhead for softmax
-// probabilities (a denormal p is 0 for every purpose here)
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// accumulator register i <-> row offset within a 32x32 tile for lane half h
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 struct Strides {
   int64_t b, s, h;  // element strides; d is unit stride
 };
 
-// Stage a [rows=ROWS][D] tile of 16-byte chunks from global into registers (each thread owns
-// ROWS*(D/8)/threads chunks), then into swizzled LDS. Rows at or beyond `nrows_valid` read as zeros.
+// mf::RowStager for a [ROWS][D] tile, kept as a local copy for two reasons: it has no bounds test
+// on the chunk index (ROWS * CH is a multiple of the thread count), and its store() evaluates the
+// XOR term of mf::soff BEFORE the row offset, where mf::soff evaluates it after -- hipcc schedules
+// the non-DMA forward kernels differently for the two orders. Merge the two when those kernels are
+// next re-measured.
 template <int ROWS, int NWAVES, int D>
 struct Stager {
   static constexpr int CH = D / 8;
@@ -174,11 +98,12 @@ struct Stager {
 #pragma unroll
     for (int i = 0; i < N; ++i) {
       const int c = threadIdx.x + i * NWAVES * 64;
-      *reinterpret_cast<u32x4*>(lds + soff<D>(c / CH, c % CH)) = r[i];
+      const int row = c / CH, ch = c % CH;
+      const int f = (((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1);
+      *reinterpret_cast<u32x4*>(lds + (row * (2 * D) + 16 * (ch ^ f))) = r[i];
     }
   }
 };
-
 
 // Block-sparse attention (reference ops/sparse_attention: Triton SDD/DSD matmuls + block softmax):
 // a uint8 layout [H, nb, nb] over blk x blk blocks (blk in {16, 32, 64, 128, ...}, a multiple of 16)
@@ -232,25 +157,15 @@ __device__ __forceinline__ void map_block(int nblk, int BH, bool heavy_last_inde
 // (the swizzle is an involution: position c' of row `row` holds logical chunk c' ^ f(row)).
 // =============================================================================================
 //
-// Issued from inline asm, not __builtin_amdgcn_global_load_lds: the compiler's wait-count pass
-// cannot tell a builtin DMA's LDS writes from the ring's LDS reads, so it put an `s_waitcnt
-// vmcnt(0)` before the first ds_read after every issue -- each dK/dV tile waited for the NEXT
-// tile's load before its first MFMA (no prefetch at all), and dQ before its dQ MFMAs. Completion is
-// tracked by hand instead: every consumer runs vm_wait_all() + a barrier before it reads a slot.
+// Issued with mf::glds16_m0 / glds4_m0, the inline-asm form (sxe_mfma.h says why): the loads stay in
+// flight across the ring's ds_reads, and every consumer runs vm_wait_all() + a barrier before it
+// reads a slot.
 extern __shared__ __attribute__((aligned(16))) char smem[];  // every kernel's dynamic LDS
 // M0 value of a wave-uniform pointer into smem: the symbol's LDS address plus the byte offset (a
 // generic-to-LDS cast of the pointer itself costs a 64-bit null check per DMA instruction)
 __device__ __forceinline__ unsigned lds_addr(const char* p) {
   return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem +
                                         (unsigned)(p - smem));
-}
-__device__ __forceinline__ void glds16(const void* gsrc, char* lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds_addr(lds_wave_base)), "v"(gsrc)
-               : "memory", "m0");
-}
-__device__ __forceinline__ void glds4(const void* gsrc, char* lds_wave_base) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(lds_addr(lds_wave_base)), "v"(gsrc)
-               : "memory", "m0");
 }
 template <int ROWS, int D, int NWV = NW>
 __device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t row_stride, int row0, char* lds) {
@@ -263,14 +178,9 @@ __device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t ro
     const int row = RPK * n + lane / CH;
     const int cpos = lane % CH;
     const int ch = cpos ^ ((((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1));
-    glds16(base + (int64_t)(row0 + row) * row_stride + ch * 8, lds + n * 1024);
+    glds16_m0(base + (int64_t)(row0 + row) * row_stride + ch * 8, lds_addr(lds + n * 1024));
   }
 }
-// s_waitcnt vmcnt(0) through the builtin (expcnt / lgkmcnt fields left at their maxima), not inline
-// asm: the compiler's wait-count pass then knows every load it tracks has landed, so it does not
-// keep counting the operand loads issued before a tile loop as pending inside the loop (where its
-// counted waits would also wait for the hand-tracked LDS-DMA below)
-__device__ __forceinline__ void vm_wait_all() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
 
 // =============================================================================================
@@ -367,7 +277,7 @@ __device__ __forceinline__ void fwd_tile(const LaneOffs<D>& lo, const char* kt, 
 template <int D, int NWF>
 constexpr int fwd_min_waves() { return D >= 256 ? 1 : 8 / NWF; }
 
-// DMA: K/V tiles go straight to LDS (global_load_lds from inline asm, see glds16) instead of through
+// DMA: K/V tiles go straight to LDS (global_load_lds from inline asm, see tile_glds) instead of through
 // the register Stager; head dim 256 always (staging registers would not fit next to its 128
 // accumulator + 64 Q-fragment registers), smaller head dims by default (SXE_FA_FWD_DMA=0 selects the
 // register Stager: 4-7 % slower at D 128, B4 S2048 to B1 S32k, equal at D 64 --
@@ -794,7 +704,7 @@ __global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>()))
     tile_glds<QT, D, NWK>(dout + b * dos.b + hq * dos.h, dos.s, qt0, slot + G_::TILE);
     if (w == 0) {  // 64 lanes x 4 B: lse[32] then delta[32]
       const int64_t lr = ((int64_t)b * H + hq) * Sq + qt0 + (lane & 31);
-      glds4(lane < 32 ? (const void*)(lse + lr) : (const void*)(delta + lr), slot + 2 * G_::TILE);
+      glds4_m0(lane < 32 ? (const void*)(lse + lr) : (const void*)(delta + lr), lds_addr(slot + 2 * G_::TILE));
     }
   };
   if constexpr ((PART & 2) != 0) tile_glds<KB, D, NWK>(vp, vs.s, kb * KB, vblk);

@@ -22,33 +22,24 @@
 // one group's barrier/wait/read latency hides under the other's MFMAs.
 // Block order: XCD-aware remap + GROUP_M super-rows so blocks on one XCD share A/B tiles in L2.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace wg {
+using namespace mf;  // types, ROWB (128 bf16 per LDS row), lds_tr, acc_row, glds16_m0, vm_wait
 
 constexpr int BM = 256, BN = 256, SLAB = 16;
 constexpr int NWAVE = 8, NTHR = NWAVE * 64;
-constexpr int ROWB = 256;                   // bytes per LDS row (128 bf16)
 constexpr int HALF = SLAB * ROWB;           // one [16][128] half slab = 4 KiB
 constexpr int SLOT = 4 * HALF;              // A (2 halves) + B (2 halves) = 16 KiB
 constexpr int GROUP_M = 8;  // default super-row height (runtime argument of the kernels)
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // LDS image of a [k][128] half tile: 16-byte chunk ch of row r sits at chunk position ch ^ swz(r).
 // Only transposed reads touch it: one ds_read_b64_tr_b16 covers rows r0+q (q = 0..3) x 64 bytes per
 // 32-lane half, and the XOR by (q << 2) puts those four rows on four different 64-byte bank
 // groups (conflict-free); the DMA writes whole 256-byte rows and cannot conflict.
 __device__ __forceinline__ int swz(int row) { return (row & 3) << 2; }
-
-__device__ __forceinline__ i16x4 lds_tr(const char* base, int byte_off) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) i16x4*)(const_cast<char*>(base) + byte_off));
-}
 
 // MFMA operand (A or B of 32x32x16) from a row-major [k][128] LDS half tile, transposed: lane gets
 // column 32*dt + (lane&31); element j of lane half h <- k row row0 + 8*(j>>2) + 4h + (j&3).
@@ -64,20 +55,12 @@ __device__ __forceinline__ int frag_off(int dt, int lane) {
 }
 
 __device__ __forceinline__ bf16x8 frag_at(const char* lane_base, int row0) {
-  i16x4 lo = lds_tr(lane_base, row0 * ROWB);
-  i16x4 hi = lds_tr(lane_base, (row0 + 8) * ROWB);
-  const i16x8 c = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, c);
+  return tr_pair(lds_tr(lane_base, row0 * ROWB), lds_tr(lane_base, (row0 + 8) * ROWB));
 }
 
-// LDS-DMA issued from inline asm: hipcc's waitcnt pass cannot see it, so it does not put a
-// conservative `s_waitcnt vmcnt(0)` in front of every ds_read of the ring (it did with the
-// builtin: the whole prefetch drained each K-step). Completion is tracked by the explicit counted
-// vmcnt + barrier in the main loop. `lds` is the wave-uniform LDS byte address (M0).
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds) {
-  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(lds), "v"(gsrc) : "memory", "m0");
-}
-
+// The slabs are loaded with mf::glds16_m0, the inline-asm LDS-DMA (sxe_mfma.h says why); completion
+// is tracked by the counted vm_wait + barrier in the main loop.
+//
 // Per-thread DMA source/destination of one slab. Wave w moves 4 k rows x 256 bytes of A-half
 // (w>>2)&1 (first instruction) and of B-half (w>>2)&1 (second): rows 4*(w&3) + (lane>>4) of the
 // slab, 16-byte chunk (lane&15) ^ swz(row). Slab j is the same pattern shifted by 16j rows (a
@@ -104,11 +87,9 @@ __device__ __forceinline__ DmaPlan dma_plan(const unsigned short* A, int64_t lda
 
 __device__ __forceinline__ void load_slab(const DmaPlan& d, int64_t lda, int64_t ldb, int slab, int slot) {
   const int r = SLAB * slab;
-  glds16(d.a + (int64_t)r * lda, d.lds_a + slot * SLOT);
-  glds16(d.b + (int64_t)r * ldb, d.lds_b + slot * SLOT);
+  glds16_m0(d.a + (int64_t)r * lda, d.lds_a + slot * SLOT);
+  glds16_m0(d.b + (int64_t)r * ldb, d.lds_b + slot * SLOT);
 }
-
-__device__ __forceinline__ int acc_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // Two K segments (A, B) rows [0, 16 ns1) then (A2, B2) rows [0, K - 16 ns1), same leading dims: the
 // product over the concatenated token axis without materialising the concatenation (the deferred
@@ -189,7 +170,7 @@ __global__ void __launch_bounds__(NTHR, 1) wgrad_kernel(const unsigned short* __
   // prologue: slabs 0 .. D-1, then the first phase's fragments
 #pragma unroll
   for (int j = 0; j < D; ++j) load_any(j, j);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT) : "memory");
+  vm_wait<WAIT>();
   __builtin_amdgcn_s_barrier();
   read_frags(0, fa[0], fb[0]);
   if (STAGGER && __builtin_amdgcn_readfirstlane(wr) == 1) __builtin_amdgcn_s_barrier();
@@ -199,9 +180,9 @@ __global__ void __launch_bounds__(NTHR, 1) wgrad_kernel(const unsigned short* __
       // the surplus DMA of the last D phases (clamped to the last slab) lands in consumed slots
       if (!NODMA) load_any(min(s0 + j + D, ns - 1), (j + D) % R);
       if (NODMA)  // ablation (variant 3): the ring is never refilled -- MFMA + LDS + barrier ceiling
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        vm_wait<0>();
       else
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT) : "memory");
+        vm_wait<WAIT>();
       __builtin_amdgcn_s_barrier();
       read_frags((j + 1) % R, fa[(j + 1) & 1], fb[(j + 1) & 1]);
       mma(fa[j & 1], fb[j & 1]);
@@ -211,7 +192,7 @@ __global__ void __launch_bounds__(NTHR, 1) wgrad_kernel(const unsigned short* __
   if (STAGGER && __builtin_amdgcn_readfirstlane(wr) == 0) __builtin_amdgcn_s_barrier();
   // ---- epilogue: C (+)= alpha * acc, two accumulator tiles (32 values / lane) per batch so the
   // C reads are in flight together instead of one dependent round trip per value
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   const int h = lane >> 5, col = lane & 31;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -309,7 +290,7 @@ __global__ void __launch_bounds__(NTHR, 1) kernel(const unsigned short* __restri
       const int64_t rows = (int64_t)SLAB * slab + 4 * rq;
       const unsigned short* src = op == 0 ? P.a + rows * lda + half * 128 : P.b + rows * ldb + half * 128;
       const unsigned dst = __builtin_amdgcn_readfirstlane(pl.lds + slot * SLOT + (op * 2 + half) * HALF + 4 * rq * ROWB);
-      glds16(src, dst);
+      glds16_m0(src, dst);
     }
   };
   // fragment bases: A half wr (columns wr*128 + 32i), B half wc (columns wc*128 + 32j); slots
@@ -347,20 +328,21 @@ __global__ void __launch_bounds__(NTHR, 1) kernel(const unsigned short* __restri
   const int ns = K / SLAB;  // a multiple of R (host check)
 #pragma unroll
   for (int j = 0; j < D; ++j) load_slab(j, j);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(WAIT) : "memory");
+  vm_wait<WAIT>();
   __builtin_amdgcn_s_barrier();
   read_frags(0, fa[0], fb[0]);
   for (int s0 = 0; s0 < ns; s0 += R) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {  // phase s = s0 + j: slab s in slot j
       load_slab(min(s0 + j + D, ns - 1), (j + D) % R);  // surplus DMA at the end lands in consumed slots
+      // vm_wait<WAIT>() and the lgkmcnt wait in ONE asm statement: nothing is scheduled between them
       asm volatile("s_waitcnt vmcnt(%0)\n\ts_waitcnt lgkmcnt(0)" ::"n"(WAIT) : "memory");
       __builtin_amdgcn_s_barrier();
       read_frags((j + 1) % R, fa[(j + 1) & 1], fb[(j + 1) & 1]);
       mma(fa[j & 1], fb[j & 1]);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  vm_wait<0>();
   const int h = lane >> 5, col = lane & 31;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {

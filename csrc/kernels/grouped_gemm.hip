@@ -75,7 +75,7 @@ struct QStager {
           }
           v[e] = (__bf16)((float)q * sc[i]);
         }
-        *reinterpret_cast<bf16x8*>(lds + soff(row, ch * (EPC / 8) + o)) = v;
+        *reinterpret_cast<bf16x8*>(lds + soff<BK>(row, ch * (EPC / 8) + o)) = v;
       }
     }
   }
@@ -132,9 +132,9 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_kernel(const unsigned sh
     for (int ks = 0; ks < BK / 16; ++ks) {
       bf16x8 a[2], b[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = lds_row16(lA, wm * 64 + i * 32 + l32, 2 * ks + h);
+      for (int i = 0; i < 2; ++i) a[i] = lds_row16<BK>(lA, wm * 64 + i * 32 + l32, 2 * ks + h);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = lds_row16(lB, wn * 64 + j * 32 + l32, 2 * ks + h);
+      for (int j = 0; j < 2; ++j) b[j] = lds_row16<BK>(lB, wn * 64 + j * 32 + l32, 2 * ks + h);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -168,13 +168,6 @@ constexpr int BM = 256, BN = 256, BKD = 64;
 constexpr int TILE = BM * BKD * 2;           // 32 KiB per operand per stage
 constexpr int STAGE = 2 * TILE;
 __device__ __forceinline__ int sw(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
 
 // WN = waves along N (2 -> 4 waves of 128 x 128; 4 -> 8 waves of 128 x 64, two per SIMD -- the
 // default: 800-903 TF/s vs 713-853 for 4 waves and 472-600 for the 128 x 128 kernel at 1024-4096
@@ -227,7 +220,7 @@ __global__ void __launch_bounds__(128 * WN, 1) grouped_gemm_dp_kernel(const unsi
   const int nk = K / BKD;
   issue(smem, 0);
   for (int kb = 0; kb < nk; ++kb) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    vm_wait<0>();
     raw_barrier();  // stage kb landed for every wave; every wave is done with stage kb - 1
     if (kb + 1 < nk) issue(smem + ((kb + 1) & 1) * STAGE, kb + 1);
     const char* ba = smem + (kb & 1) * STAGE;
@@ -321,9 +314,9 @@ __global__ void __launch_bounds__(NTHR, 2) grouped_gemm_q_kernel(const unsigned 
     for (int ks = 0; ks < BK / 16; ++ks) {
       bf16x8 a[2], b[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) a[i] = lds_row16(lA, wm * 64 + i * 32 + l32, 2 * ks + h);
+      for (int i = 0; i < 2; ++i) a[i] = lds_row16<BK>(lA, wm * 64 + i * 32 + l32, 2 * ks + h);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) b[j] = lds_row16(lB, wn * 64 + j * 32 + l32, 2 * ks + h);
+      for (int j = 0; j < 2; ++j) b[j] = lds_row16<BK>(lB, wn * 64 + j * 32 + l32, 2 * ks + h);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 2; ++i)

@@ -26,15 +26,12 @@
 // XCD-major: the 8 XCDs each take a contiguous range of output tiles (M fastest), so the weight
 // column tiles a workgroup streams are shared through its XCD's L2.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace mx {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+using mf::i32x8, mf::f32x16, mf::u32x4, mf::u32x2;
 
 constexpr int BK = 128;
 constexpr int SA = 128 + 16;  // padded LDS row stride of the fp8 activation tile
@@ -55,6 +52,8 @@ struct BLayout {
   static constexpr int LB = 4 * BITS;   // bytes one lane feeds per MFMA (32 elements)
 };
 
+// Register stager like mf::RowStager (sxe_mfma.h), but for byte rows of CPR chunks at a padded,
+// unswizzled LDS stride
 template <int ROWS, int CPR, int STRIDE, int NTHR>
 struct Stager {
   static constexpr int N = (ROWS * CPR + NTHR - 1) / NTHR;
@@ -308,17 +307,7 @@ template <int FB, int BN, int NWV = 4> struct L {
 __device__ __forceinline__ int fA(int r) { return (r >> 1) & 7; }
 template <int RP> __device__ __forceinline__ int fB(int r) { return RP == 64 ? ((r >> 2) & 3) : ((r >> 1) & 7); }
 
-template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-__device__ __forceinline__ void glds16(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const void* g, char* l) {
-  __builtin_amdgcn_global_load_lds(g, (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
+using mf::vm_wait, mf::raw_barrier, mf::glds16, mf::glds4;  // the builtin LDS-DMA form (sxe_mfma.h)
 
 template <int FB, int BN, int NWV>
 __device__ __forceinline__ void issue_stage(char* buf, const uint8_t* Xq, const uint8_t* Xs, const uint8_t* Wq,

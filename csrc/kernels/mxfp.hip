@@ -19,12 +19,13 @@
 // the bf16 high / low bytes), byte masks and v_bfi -- ~2 VALU per weight for FP4, ~4 for FP6 --
 // so the kernel stays HBM-bound while reading 1/4 (FP4) or 3/8 (FP6) of the bf16 bytes.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace mx {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+using mf::i16x8;  // bf16 bit patterns
 
 // ---------------------------------------------------------------------------- element codecs
 __device__ __forceinline__ int fp4_index(float a) {  // a >= 0, already scaled into [0, 6]
@@ -136,10 +137,10 @@ __device__ __forceinline__ void fp6x4(unsigned se, unsigned m, unsigned& d01, un
   interleave(H, L, d01, d23);
 }
 
-__device__ __forceinline__ bf16x8 as_bf16x8(const unsigned (&o)[4]) {
+__device__ __forceinline__ i16x8 as_bf16x8(const unsigned (&o)[4]) {
   typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
   u32x4v v = {o[0], o[1], o[2], o[3]};
-  return __builtin_bit_cast(bf16x8, v);
+  return __builtin_bit_cast(i16x8, v);
 }
 
 // ------------------------------------------------------------------- weight-only skinny GEMM
@@ -170,10 +171,10 @@ __global__ void __launch_bounds__(NW * 64) skinny_fpxw_kernel(const unsigned sho
     uint4 av = (wok && in) ? *reinterpret_cast<const uint4*>(arow + k / 2) : uint4{0u, 0u, 0u, 0u};
     uint2 bv = uint2{0u, 0u};
     if constexpr (BITS == 6) bv = (wok && in) ? *reinterpret_cast<const uint2*>(brow + k / 4) : uint2{0u, 0u};
-    bf16x8 xs[4];
+    i16x8 xs[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      xs[t] = (xok && in) ? *reinterpret_cast<const bf16x8*>(xrow + k + 8 * t) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      xs[t] = (xok && in) ? *reinterpret_cast<const i16x8*>(xrow + k + 8 * t) : i16x8{0, 0, 0, 0, 0, 0, 0, 0};
     const unsigned aw[4] = {av.x, av.y, av.z, av.w};
 #pragma unroll
     for (int t = 0; t < 4; ++t) {

@@ -26,6 +26,7 @@
 //  * causal masking by absolute position (chunked prefill / speculative tokens just work), sliding
 //    windows skip the key chunks they mask entirely.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
@@ -123,21 +124,11 @@ struct Args {
   int* counters;   // [S * nkv] zeroed split-arrival counters: the last split of a (seq, kv head) merges; or null
 };
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short i16x4 __attribute__((ext_vector_type(4)));
-typedef short i16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// the V image is the swizzled [rows][D bf16] tile of sxe_mfma.h (soff), read transposed (lds_tr)
+using mf::bf16x8, mf::u32x4, mf::soff, mf::lds_tr, mf::tr_pair, mf::glds16, mf::vm_wait;
 
 __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-
-// byte offset of 16-byte chunk `ch` of row `row` in a swizzled [rows][D bf16] image (see flash_attn.hip)
-template <int D>
-__device__ __forceinline__ int soff(int row, int ch) {
-  constexpr int CH = D / 8;
-  const int f = (((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1);
-  return row * (2 * D) + 16 * (ch ^ f);
 }
 
 // first key row of lane group g's 4-row block in a 16-key tile (C rows 4g..4g+3 <-> keys kperm(g)+e):
@@ -237,9 +228,7 @@ __global__ __launch_bounds__(256) void paged_attn_kernel(Args a) {
           const int row = RPK * n + lane / CH;
           const int cpos = lane % CH;
           const int ch = cpos ^ ((((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1));
-          __builtin_amdgcn_global_load_lds(
-              (const __attribute__((address_space(1))) void*)(a.cache + koff_lds[wave][row] + half_stride + ch * 8),
-              (__attribute__((address_space(3))) void*)(vimg + n * 1024), 16, 0, 0);
+          glds16(a.cache + koff_lds[wave][row] + half_stride + ch * 8, vimg + n * 1024);
         }
       }
       // ---- S^T = K Q^T: lane holds keys 16t + kperm(g) + e of row i ------------------------------
@@ -280,7 +269,7 @@ __global__ __launch_bounds__(256) void paged_attn_kernel(Args a) {
       m = mn;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) o[dt] *= alpha;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's V image has landed
+      vm_wait<0>();  // this wave's V image has landed
       __builtin_amdgcn_wave_barrier();
       // ---- O^T += V^T P^T over key-tile pairs: P^T straight from the score registers -------------
 #pragma unroll
@@ -296,12 +285,9 @@ __global__ __launch_bounds__(256) void paged_attn_kernel(Args a) {
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt) {
           const int ch = 2 * dt + (p4 >> 1);
-          const i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) i16x4*)(vimg + soff<D>(r0, ch) + 8 * (p4 & 1)));
-          const i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-              (__attribute__((address_space(3))) i16x4*)(vimg + soff<D>(r0 + 16, ch) + 8 * (p4 & 1)));
-          const i16x8 va = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          o[dt] = mfma16(__builtin_bit_cast(bf16x8, va), pb, o[dt]);
+          const bf16x8 va = tr_pair(lds_tr(vimg + soff<D>(r0, ch), 8 * (p4 & 1)),
+                                    lds_tr(vimg + soff<D>(r0 + 16, ch), 8 * (p4 & 1)));
+          o[dt] = mfma16(va, pb, o[dt]);
         }
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);  // the V image is read before the next chunk overwrites it

@@ -16,12 +16,13 @@
 // is 4 wave-instructions of 1 KiB, each fully coalesced. Rows are opaque bytes, so every dtype
 // uses the same code; only ``add`` (an elementwise sum) needs the type.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace rows {
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using mf::u32x4;
 
 template <typename I, DT T, bool ADD>
 __global__ void __launch_bounds__(256) gather_kernel(const u32x4* __restrict__ src, const u32x4* __restrict__ add,

@@ -14,15 +14,14 @@
 // v_mfma_f32_16x16x32_bf16 (lane group g = lane >> 4 covers K = 32 g .. 32 g + 31 of the step, so
 // each lane's codes are exactly one scale block). Cross-wave partial sums are reduced in LDS.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace sdq {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+using mf::bf16x8, mf::u32x4, mf::u32x2;
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 enum Fmt : int { E4M3 = 0, E3M2 = 3, E2M1 = 4, I8 = 8, I4 = 9 };
 __host__ __device__ constexpr int fmt_bytes32(int f) {  // bytes per 32 codes

@@ -19,17 +19,18 @@
 //    flight, so the norm / gated-activation launches (4-5 us each at batch 1, latency-bound) are
 //    gone from the decode layer. Workgroup 0 also writes the new residual stream h = x + res.
 #include "sxe_common.h"
+#include "sxe_mfma.h"
 #include <torch/library.h>
 
 namespace sxe {
 namespace sg {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
+using mf::i16x8;  // bf16 bit patterns
 constexpr int kSS = 256;  // K per super-step per wave
 
 struct Frag {
-  bf16x8 w[8];
-  bf16x8 x[8];
+  i16x8 w[8];
+  i16x8 x[8];
 };
 
 // nt: non-temporal weight loads (`global_load ... nt`) -- a decode GEMM reads each weight byte once,
@@ -42,16 +43,16 @@ __device__ __forceinline__ void load_w(Frag& f, const unsigned short* __restrict
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const int k = kbase + s * 32;
-    const bf16x8* p = reinterpret_cast<const bf16x8*>(wrow + k);
+    const i16x8* p = reinterpret_cast<const i16x8*>(wrow + k);
     if (wok && k < K) f.w[s] = NT ? __builtin_nontemporal_load(p) : *p;
-    else f.w[s] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    else f.w[s] = i16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 }
 __device__ __forceinline__ void load_x(Frag& f, const unsigned short* __restrict xrow, bool xok, int kbase, int K) {
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     const int k = kbase + s * 32;
-    f.x[s] = (xok && k < K) ? *reinterpret_cast<const bf16x8*>(xrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    f.x[s] = (xok && k < K) ? *reinterpret_cast<const i16x8*>(xrow + k) : i16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 }
 
@@ -358,10 +359,10 @@ inline int pick_nw(int tiles, int ss_total, int min_ss, int wg8_per_cu) {
 // K = k0 + 64 j + 16 g + 8 h + [0, 8) for lane group g, for weights and activations alike.
 constexpr int kSS8 = 512;
 
-__device__ __forceinline__ bf16x8 fp8x8_to_bf16(uint2 w) {
+__device__ __forceinline__ i16x8 fp8x8_to_bf16(uint2 w) {
   // byte-selected v_cvt_f32_fp8 (byte b of the word -> element b): explicit order, e4m3 is exact
   // in bf16 so the top half of the f32 bit pattern is the bf16 value
-  bf16x8 r;
+  i16x8 r;
 #define SXE_FP8_BYTE(word, b) (short)(__builtin_bit_cast(unsigned int, __builtin_amdgcn_cvt_f32_fp8((int)(word), b)) >> 16)
   r[0] = SXE_FP8_BYTE(w.x, 0);
   r[1] = SXE_FP8_BYTE(w.x, 1);
@@ -406,15 +407,15 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_fp8w_kernel(const unsigne
   for (int i = 0; i < ss_per_wave; ++i) {
     const int k0 = (wave * ss_per_wave + i) * kSS8 + 16 * g;
     uint4 wv[8];
-    bf16x8 xa[8], xb[8];
+    i16x8 xa[8], xb[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int k = k0 + 64 * j;
       const bool in = k < K;
       if (MODE != PRO_NONE && i == 0) wv[j] = wv0[j];
       else wv[j] = (wok && in) ? *reinterpret_cast<const uint4*>(wrow + k) : uint4{0u, 0u, 0u, 0u};
-      xa[j] = (xok && in) ? *reinterpret_cast<const bf16x8*>(xrow + k) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      xb[j] = (xok && in) ? *reinterpret_cast<const bf16x8*>(xrow + k + 8) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      xa[j] = (xok && in) ? *reinterpret_cast<const i16x8*>(xrow + k) : i16x8{0, 0, 0, 0, 0, 0, 0, 0};
+      xb[j] = (xok && in) ? *reinterpret_cast<const i16x8*>(xrow + k + 8) : i16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
