@@ -20,6 +20,7 @@
 // so the kernel stays HBM-bound while reading 1/4 (FP4) or 3/8 (FP6) of the bf16 bytes.
 #include "sxe_common.h"
 #include "sxe_mfma.h"
+#include "sxe_skinny.h"
 #include <torch/library.h>
 
 namespace sxe {
@@ -194,15 +195,7 @@ __global__ void __launch_bounds__(NW * 64) skinny_fpxw_kernel(const unsigned sho
   red[wave][lane] = acc;
   __syncthreads();
   if (wave == 0) {
-    f32x4 t = red[0][lane];
-#pragma unroll
-    for (int v = 1; v < NW; ++v) {
-      const f32x4 u = red[v][lane];
-      t[0] += u[0];
-      t[1] += u[1];
-      t[2] += u[2];
-      t[3] += u[3];
-    }
+    const f32x4 t = skinny::reduce_waves(red, lane);
     if (n < N) {
       const float sc = wscale[n];
       const float b = bias ? bf16_to_f32(bias[n]) : 0.f;
@@ -331,31 +324,21 @@ static void check_fpxw(const at::Tensor& wa, const c10::optional<at::Tensor>& wb
 
 at::Tensor skinny_gemm_fpxw(const at::Tensor& x, const at::Tensor& wa, const c10::optional<at::Tensor>& wb,
                             const at::Tensor& wscale, const c10::optional<at::Tensor>& bias, int64_t bits) {
-  SXE_CHECK_CUDA(x);
-  SXE_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "skinny_gemm_fpxw: bf16 x [M, K]");
+  constexpr const char* op = "skinny_gemm_fpxw";
+  const unsigned short* xp = skinny::check_x(x, op, 16);
   const int M = x.size(0), K = x.size(1), N = wa.size(0);
   check_fpxw(wa, wb, wscale, bits, K);
-  SXE_CHECK(M >= 1 && M <= 16, "skinny_gemm_fpxw: 1 <= M <= 16");
-  SXE_CHECK(x.stride(0) % 8 == 0 && (reinterpret_cast<uintptr_t>(x.data_ptr()) & 15) == 0,
-            "skinny_gemm_fpxw: 16-byte aligned activation rows");
-  const unsigned short* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, "bias: bf16 [N]");
-    bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-  }
+  const unsigned short* bp = skinny::bias_ptr(bias, N, op);
   auto y = at::empty({M, N}, x.options());
   if (N == 0) return y;
   c10::DeviceGuard g(x.device());
   const int steps = K / 128, tiles = (N + 15) / 16;
-  int nw = 4;
-  while (nw < 8 && (int64_t)tiles * nw < 4096 && steps >= 2 * nw) nw *= 2;
-  const int spw = (steps + nw - 1) / nw;
+  const int nw = skinny::pick_nw(tiles, steps, 2, skinny::kNoRoundCap), spw = (steps + nw - 1) / nw;
   const uint8_t* bptr = bits == 6 ? wb->data_ptr<uint8_t>() : nullptr;
   const int64_t ldb = bits == 6 ? wb->stride(0) : 0;
 #define SXE_FW(B, NW)                                                                                                \
-  hipLaunchKernelGGL((mx::skinny_fpxw_kernel<B, NW>), dim3(tiles), dim3(NW * 64), 0, cur_stream(),                   \
-                     reinterpret_cast<const unsigned short*>(x.data_ptr()), x.stride(0), wa.data_ptr<uint8_t>(),      \
-                     wa.stride(0), bptr, ldb, wscale.data_ptr<float>(), bp,                                          \
+  hipLaunchKernelGGL((mx::skinny_fpxw_kernel<B, NW>), dim3(tiles), dim3(NW * 64), 0, cur_stream(), xp, x.stride(0),  \
+                     wa.data_ptr<uint8_t>(), wa.stride(0), bptr, ldb, wscale.data_ptr<float>(), bp,                  \
                      reinterpret_cast<unsigned short*>(y.data_ptr()), y.stride(0), M, N, K, spw)
   if (bits == 4) {
     if (nw == 4) SXE_FW(4, 4); else SXE_FW(4, 8);

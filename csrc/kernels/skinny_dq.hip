@@ -15,6 +15,7 @@
 // each lane's codes are exactly one scale block). Cross-wave partial sums are reduced in LDS.
 #include "sxe_common.h"
 #include "sxe_mfma.h"
+#include "sxe_skinny.h"
 #include <torch/library.h>
 
 namespace sxe {
@@ -198,13 +199,10 @@ __global__ void __launch_bounds__(NW * 64) skinny_dq_kernel(const unsigned short
 // (scales uint8 E8M0 [N, K / 32]), 8 / 9 = int8 / int4 (scales fp32 [N, K / group], group % 32 == 0)
 at::Tensor skinny_gemm_dq(at::Tensor x, at::Tensor wq, at::Tensor scales, int64_t fmt, int64_t group,
                           c10::optional<at::Tensor> bias) {
-  SXE_CHECK_CUDA(x);
+  constexpr const char* op = "skinny_gemm_dq";
   SXE_CHECK(fmt == 0 || fmt == 3 || fmt == 4 || fmt == 8 || fmt == 9, "skinny_gemm_dq: fmt 0 / 3 / 4 (MX) or 8 / 9 (int)");
-  SXE_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
-            "skinny_gemm_dq: bf16 x [M, K] with 16-byte aligned rows");
+  const unsigned short* xp = skinny::check_x(x, op, 16);
   const int64_t M = x.size(0), K = x.size(1);
-  SXE_CHECK(M >= 1 && M <= 16, "skinny_gemm_dq: 1 <= M <= 16");
   SXE_CHECK(K % 128 == 0, "skinny_gemm_dq: K must be a multiple of 128");
   const bool is_int = fmt >= 8;
   if (!is_int) group = 32;
@@ -217,22 +215,16 @@ at::Tensor skinny_gemm_dq(at::Tensor x, at::Tensor wq, at::Tensor scales, int64_
   SXE_CHECK(scales.is_cuda() && scales.is_contiguous() && scales.numel() == N * (K / group) &&
                 (is_int ? scales.scalar_type() == at::kFloat : scales.scalar_type() == at::kByte),
             "skinny_gemm_dq: scales [N, K / group] (fp32 for int, uint8 E8M0 for MX)");
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->is_cuda() && bias->is_contiguous() && bias->scalar_type() == at::kBFloat16 && bias->numel() == N,
-              "skinny_gemm_dq: bias bf16 [N]");
-  }
+  const unsigned short* b = skinny::bias_ptr(bias, N, op);
   c10::DeviceGuard guard(x.device());
   auto y = at::empty({M, N}, x.options());
   constexpr int NW = 8;
   const unsigned tiles = (unsigned)((N + 15) / 16);
   const int steps = (int)((K / 128 + NW - 1) / NW);
-  const unsigned short* b = (bias.has_value() && bias->defined()) ? reinterpret_cast<const unsigned short*>(bias->data_ptr())
-                                                                   : nullptr;
 #define SXE_SDQ(F)                                                                                                   \
-  hipLaunchKernelGGL((sdq::skinny_dq_kernel<F, NW, 1>), dim3(tiles), dim3(NW * 64), 0, cur_stream(),                \
-                     reinterpret_cast<const unsigned short*>(x.data_ptr()), x.stride(0), wq.data_ptr<uint8_t>(),     \
-                     K * by / 32, scales.data_ptr(), (int)(K / group), (int)group, b,                               \
-                     reinterpret_cast<unsigned short*>(y.data_ptr()), N, (int)M, (int)N, (int)K, steps)
+  hipLaunchKernelGGL((sdq::skinny_dq_kernel<F, NW, 1>), dim3(tiles), dim3(NW * 64), 0, cur_stream(), xp,            \
+                     x.stride(0), wq.data_ptr<uint8_t>(), K * by / 32, scales.data_ptr(), (int)(K / group),          \
+                     (int)group, b, reinterpret_cast<unsigned short*>(y.data_ptr()), N, (int)M, (int)N, (int)K, steps)
   switch (fmt) {
     case 0: SXE_SDQ(sdq::E4M3); break;
     case 3: SXE_SDQ(sdq::E3M2); break;

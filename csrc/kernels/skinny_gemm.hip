@@ -20,6 +20,7 @@
 //    gone from the decode layer. Workgroup 0 also writes the new residual stream h = x + res.
 #include "sxe_common.h"
 #include "sxe_mfma.h"
+#include "sxe_skinny.h"
 #include <torch/library.h>
 
 namespace sxe {
@@ -304,19 +305,11 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(const unsigned sho
       nxt = nx2;
     }
   }
-  // acc: C[row m = 4 g + r][col n] -- sum the 4 waves' K partials
+  // acc: C[row m = 4 g + r][col n] -- sum the NW waves' K partials
   red[wave][lane] = acc;
   __syncthreads();
   if (wave == 0) {
-    f32x4 t = red[0][lane];
-#pragma unroll
-    for (int v = 1; v < NW; ++v) {
-      const f32x4 u = red[v][lane];
-      t[0] += u[0];
-      t[1] += u[1];
-      t[2] += u[2];
-      t[3] += u[3];
-    }
+    const f32x4 t = skinny::reduce_waves(red, lane);
     if (MODE == PRO_RMS && pro.rcos != nullptr) {  // RoPE epilogue (no bias: checked on the host)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -333,23 +326,6 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_kernel(const unsigned sho
       }
     }
   }
-}
-
-// Waves per workgroup: NW = 8 (more waves streaming per CU) while the tiles still fit on the chip
-// in ONE round -- at ~150 VGPRs (bf16) one 8-wave workgroup fits per CU, at ~115 (fp8) two -- and
-// every wave keeps >= `min_ss` super-steps; otherwise NW = 4 (three / four workgroups per CU), so
-// e.g. the 384-tile QKV projection does not run a second, half-empty round of 8-wave workgroups.
-// SXE_SKINNY_NT (read per call; a captured decode graph keeps the value of its capture)
-inline int nt_loads() {
-  const char* e = std::getenv("SXE_SKINNY_NT");
-  return (e != nullptr && *e != 0 && *e != '0') ? 1 : 0;
-}
-
-inline int pick_nw(int tiles, int ss_total, int min_ss, int wg8_per_cu) {
-  int nw = 4;
-  while (nw < 8 && (int64_t)tiles * nw < 4096 && ss_total >= min_ss * nw) nw *= 2;
-  if (nw == 8 && tiles > kNumCUs * wg8_per_cu) nw = 4;
-  return nw;
 }
 
 // ---- FP8-weight variant (W8A16: e4m3 weights, per-output-row fp32 scale, bf16 activations) ----
@@ -426,15 +402,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_fp8w_kernel(const unsigne
   red[wave][lane] = acc;
   __syncthreads();
   if (wave == 0) {
-    f32x4 t = red[0][lane];
-#pragma unroll
-    for (int v = 1; v < NW; ++v) {
-      const f32x4 u = red[v][lane];
-      t[0] += u[0];
-      t[1] += u[1];
-      t[2] += u[2];
-      t[3] += u[3];
-    }
+    const f32x4 t = skinny::reduce_waves(red, lane);
     if (MODE == PRO_RMS && pro.rcos != nullptr) {  // RoPE epilogue (no bias: checked on the host)
       const float sc = wscale[n];
 #pragma unroll
@@ -455,94 +423,142 @@ __global__ __launch_bounds__(NW * 64) void skinny_gemm_fp8w_kernel(const unsigne
   }
 }
 
-// Waves per workgroup and super-steps per wave of the bf16 kernel. (A split-K variant -- K split
-// over 2-4 workgroups with a last-arrival reduction -- was measured and removed: 5.9 vs 3.7 ms per
-// batch-1 decode step, profiles/r05/decode_splitk_ab.log.)
-inline void plan(int tiles, int ss_total, int& nw, int& spw) {
-  nw = pick_nw(tiles, ss_total, 4, 1);
-  spw = (ss_total + nw - 1) / nw;
+// The compiler emits instantiations in the order of their first use. This list pins the order the
+// file has always had, so that tools/kernel_isa_diff.py can keep comparing its assembly as text when
+// only the host side below changes.
+template <int NW, int MODE, bool NT>
+constexpr auto kBf16 = skinny_gemm_kernel<NW, MODE, NT>;
+template <int NW, int MODE>
+constexpr auto kFp8 = skinny_gemm_fp8w_kernel<NW, MODE>;
+[[maybe_unused]] static const void* const kEmissionOrder[] = {
+    (void*)kBf16<4, 0, true>, (void*)kBf16<8, 0, true>, (void*)kBf16<4, 0, false>, (void*)kBf16<8, 0, false>,
+    (void*)kFp8<4, 0>,        (void*)kFp8<8, 0>,
+    (void*)kBf16<4, 1, true>, (void*)kBf16<4, 1, false>, (void*)kBf16<8, 1, true>, (void*)kBf16<8, 1, false>,
+    (void*)kBf16<4, 2, true>, (void*)kBf16<4, 2, false>, (void*)kBf16<8, 2, true>, (void*)kBf16<8, 2, false>,
+    (void*)kFp8<4, 1>,        (void*)kFp8<8, 1>,         (void*)kFp8<4, 2>,        (void*)kFp8<8, 2>,
+    (void*)kBf16<4, 3, true>, (void*)kBf16<4, 3, false>, (void*)kBf16<8, 3, true>, (void*)kBf16<8, 3, false>,
+    (void*)kFp8<4, 3>,        (void*)kFp8<8, 3>};
+
+// ---- host side: one launch path for every entry point ------------------------------------------
+// The resolved operands of one launch. x is nullptr under PRO_MERGE (the input comes from ProArgs).
+struct Operands {
+  const unsigned short* x;
+  int64_t ldx;
+  const void* w;  // bf16 [N, K], or e4m3 bytes when wscale != nullptr
+  int64_t ldw;
+  const float* wscale;
+  const unsigned short* bias;
+  unsigned short* y;
+  int64_t ldy;
+  int M, N, K;
+  size_t lds;  // dynamic LDS: the M x K input a PRO_* prologue builds; 0 for PRO_NONE
+};
+
+// Checks w / wscale / bias, allocates y [M, N] and fills every field of `o` but x / ldx / lds.
+static at::Tensor resolve(const char* op, const at::Tensor& w, const c10::optional<at::Tensor>& wscale,
+                          const c10::optional<at::Tensor>& bias, int M, const at::TensorOptions& like, Operands& o) {
+  const bool fp8 = wscale.has_value() && wscale->defined();
+  skinny::check_w_rows(w, op);
+  SXE_CHECK(fp8 ? w.element_size() == 1 : w.scalar_type() == at::kBFloat16, op, ": w bf16, or fp8 bytes with wscale");
+  SXE_CHECK(w.size(1) % (fp8 ? 16 : 8) == 0, op, ": K must allow 16-byte loads");
+  auto y = at::empty({M, w.size(0)}, like.dtype(at::kBFloat16));
+  o.w = w.data_ptr(), o.ldw = w.stride(0);
+  o.M = M, o.N = w.size(0), o.K = w.size(1);
+  o.wscale = fp8 ? skinny::row_scale_ptr(*wscale, o.N, op) : nullptr;
+  o.bias = skinny::bias_ptr(bias, o.N, op);
+  o.y = reinterpret_cast<unsigned short*>(y.data_ptr()), o.ldy = y.stride(0);
+  return y;
+}
+
+// The M x K bf16 input of a PRO_* mode must fit the dynamic-LDS budget.
+static size_t act_bytes(const Operands& o, const char* op) {
+  const size_t lds = (size_t)o.M * o.K * 2;
+  SXE_CHECK(lds <= skinny::kMaxDynamicLds, op, ": M x K input exceeds the LDS budget");
+  return lds;
+}
+
+// SXE_SKINNY_NT (read per call; a captured decode graph keeps the value of its capture)
+inline int nt_loads() {
+  const char* e = std::getenv("SXE_SKINNY_NT");
+  return (e != nullptr && *e != 0 && *e != '0') ? 1 : 0;
+}
+
+template <int V>
+using Int = std::integral_constant<int, V>;
+
+// bf16 weights: NW from the plan, NT from ProArgs. (A split-K variant -- K split over 2-4 workgroups
+// with a last-arrival reduction -- was measured and removed: 5.9 vs 3.7 ms per batch-1 decode step,
+// profiles/r05/decode_splitk_ab.log.)
+template <int MODE>
+static void launch_bf16(const Operands& o, const ProArgs& pro) {
+  const int tiles = (o.N + 15) / 16, ss_total = (o.K + kSS - 1) / kSS;
+  const int nw = skinny::pick_nw(tiles, ss_total, 4, 1), spw = (ss_total + nw - 1) / nw;
+  auto go = [&](auto nw_c, auto nt_c) {
+    constexpr auto kernel = kBf16<decltype(nw_c)::value, MODE, decltype(nt_c)::value != 0>;
+    if constexpr (MODE != PRO_NONE) skinny::allow_max_dynamic_lds<kernel>();
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(nw * 64), o.lds, cur_stream(), o.x, o.ldx,
+                       static_cast<const unsigned short*>(o.w), o.ldw, o.bias, o.y, o.ldy, o.M, o.N, o.K, spw, pro);
+  };
+  if (nw == 4) pro.nt ? go(Int<4>{}, Int<1>{}) : go(Int<4>{}, Int<0>{});
+  else pro.nt ? go(Int<8>{}, Int<1>{}) : go(Int<8>{}, Int<0>{});
+}
+
+// fp8 weights: NW from the plan (two 8-wave workgroups fit per CU, and 2 super-steps per wave do).
+template <int MODE>
+static void launch_fp8(const Operands& o, const ProArgs& pro) {
+  const int tiles = (o.N + 15) / 16, ss_total = (o.K + kSS8 - 1) / kSS8;
+  const int nw = skinny::pick_nw(tiles, ss_total, 2, 2), spw = (ss_total + nw - 1) / nw;
+  auto go = [&](auto nw_c) {
+    constexpr auto kernel = kFp8<decltype(nw_c)::value, MODE>;
+    if constexpr (MODE != PRO_NONE) skinny::allow_max_dynamic_lds<kernel>();
+    hipLaunchKernelGGL(kernel, dim3(tiles), dim3(nw * 64), o.lds, cur_stream(), o.x, o.ldx,
+                       static_cast<const uint8_t*>(o.w), o.ldw, o.wscale, o.bias, o.y, o.ldy, o.M, o.N, o.K, spw, pro);
+  };
+  if (nw == 4) go(Int<4>{});
+  else go(Int<8>{});
+}
+
+// The one place where the run-time mode becomes the compile-time MODE and the weight kind is chosen.
+// `y` is the output tensor behind o.y.
+static void launch(int mode, const Operands& o, ProArgs pro, const at::Tensor& y) {
+  if (o.N == 0) return;
+  c10::DeviceGuard gd(y.device());
+  pro.nt = nt_loads();
+  auto go = [&](auto mode_c) {
+    constexpr int MODE = decltype(mode_c)::value;
+    if (o.wscale != nullptr) launch_fp8<MODE>(o, pro);
+    else launch_bf16<MODE>(o, pro);
+  };
+  switch (mode) {
+    case PRO_NONE: go(Int<PRO_NONE>{}); break;
+    case PRO_RMS: go(Int<PRO_RMS>{}); break;
+    case PRO_SWIGLU: go(Int<PRO_SWIGLU>{}); break;
+    default: go(Int<PRO_MERGE>{}); break;
+  }
+  SXE_LAUNCH_CHECK();
 }
 
 }  // namespace sg
 
 // x [M, K] (row stride free, unit column stride), w [N, K] contiguous rows, bias [N] or None.
 at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& bias) {
-  SXE_CHECK_CUDA(x);
-  SXE_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "skinny_gemm: bf16 only");
-  SXE_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "skinny_gemm: x [M, K], w [N, K]");
-  SXE_CHECK(x.stride(1) == 1 && w.stride(1) == 1, "skinny_gemm: unit stride along K");
-  const int M = x.size(0), N = w.size(0), K = x.size(1);
-  SXE_CHECK(M >= 1 && M <= 16, "skinny_gemm: 1 <= M <= 16");
-  SXE_CHECK(K % 8 == 0 && x.stride(0) % 8 == 0 && w.stride(0) % 8 == 0,
-            "skinny_gemm: K and row strides must be multiples of 8 (16-byte loads)");
-  SXE_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-            "skinny_gemm: 16-byte aligned operands");
-  const unsigned short* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, "bias: bf16 [N]");
-    bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-  }
-  auto y = at::empty({M, N}, x.options());
-  if (N == 0) return y;
-  c10::DeviceGuard gd(x.device());
-  const int ss_total = (K + sg::kSS - 1) / sg::kSS;
-  const int tiles = (N + 15) / 16;
-  int nw = 4, ss_per_wave = 1;
-  sg::ProArgs pro{};
-  pro.nt = sg::nt_loads();
-  sg::plan(tiles, ss_total, nw, ss_per_wave);
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-  auto* yp = reinterpret_cast<unsigned short*>(y.data_ptr());
-#define SXE_SG_LAUNCH(NW, NT)                                                                              \
-  hipLaunchKernelGGL((sg::skinny_gemm_kernel<NW, sg::PRO_NONE, NT>), dim3(tiles), dim3(NW * 64), 0, cur_stream(), \
-                     xp, x.stride(0), wp, w.stride(0), bp, yp, y.stride(0), M, N, K, ss_per_wave, pro)
-  if (pro.nt) { if (nw == 4) SXE_SG_LAUNCH(4, true); else SXE_SG_LAUNCH(8, true); }
-  else { if (nw == 4) SXE_SG_LAUNCH(4, false); else SXE_SG_LAUNCH(8, false); }
-#undef SXE_SG_LAUNCH
-  SXE_LAUNCH_CHECK();
+  constexpr const char* op = "skinny_gemm";
+  sg::Operands o{skinny::check_x(x, op, 16), x.stride(0)};
+  auto y = sg::resolve(op, w, c10::nullopt, bias, x.size(0), x.options(), o);
+  SXE_CHECK(x.size(1) == o.K, op, ": x [M, K], w [N, K]");
+  sg::launch(sg::PRO_NONE, o, sg::ProArgs{}, y);
   return y;
 }
 
 // x [M, K] bf16, wq [N, K] e4m3 bytes (uint8 or float8_e4m3fn), wscale [N] fp32, bias [N] bf16 or None
 at::Tensor skinny_gemm_fp8w(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wscale,
                             const c10::optional<at::Tensor>& bias) {
-  SXE_CHECK_CUDA(x);
-  SXE_CHECK(x.scalar_type() == at::kBFloat16, "skinny_gemm_fp8w: bf16 activations");
-  SXE_CHECK(wq.element_size() == 1 && wq.dim() == 2 && wq.stride(1) == 1, "skinny_gemm_fp8w: wq [N, K] bytes");
-  SXE_CHECK(wscale.scalar_type() == at::kFloat && wscale.is_contiguous() && wscale.numel() == wq.size(0),
-            "skinny_gemm_fp8w: wscale fp32 [N]");
-  SXE_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.size(1) == wq.size(1), "skinny_gemm_fp8w: x [M, K]");
-  const int M = x.size(0), N = wq.size(0), K = x.size(1);
-  SXE_CHECK(M >= 1 && M <= 16, "skinny_gemm_fp8w: 1 <= M <= 16");
-  SXE_CHECK(K % 16 == 0 && wq.stride(0) % 16 == 0 && x.stride(0) % 8 == 0,
-            "skinny_gemm_fp8w: K and row strides must allow 16-byte loads");
-  SXE_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
-            "skinny_gemm_fp8w: 16-byte aligned operands");
-  const unsigned short* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, "bias: bf16 [N]");
-    bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-  }
-  auto y = at::empty({M, N}, x.options());
-  if (N == 0) return y;
-  c10::DeviceGuard gd(x.device());
-  const int ss_total = (K + sg::kSS8 - 1) / sg::kSS8;
-  const int tiles = (N + 15) / 16;
-  const int nw = sg::pick_nw(tiles, ss_total, 2, 2);
-  const int ss_per_wave = (ss_total + nw - 1) / nw;
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* wp = reinterpret_cast<const uint8_t*>(wq.data_ptr());
-  auto* yp = reinterpret_cast<unsigned short*>(y.data_ptr());
-  if (nw == 4)
-    hipLaunchKernelGGL(sg::skinny_gemm_fp8w_kernel<4>, dim3(tiles), dim3(256), 0, cur_stream(), xp, x.stride(0), wp,
-                       wq.stride(0), wscale.data_ptr<float>(), bp, yp, y.stride(0), M, N, K, ss_per_wave,
-                       sg::ProArgs{});
-  else
-    hipLaunchKernelGGL(sg::skinny_gemm_fp8w_kernel<8>, dim3(tiles), dim3(512), 0, cur_stream(), xp, x.stride(0), wp,
-                       wq.stride(0), wscale.data_ptr<float>(), bp, yp, y.stride(0), M, N, K, ss_per_wave,
-                       sg::ProArgs{});
-  SXE_LAUNCH_CHECK();
+  constexpr const char* op = "skinny_gemm_fp8w";
+  SXE_CHECK(wscale.defined(), op, ": wscale fp32 [N]");
+  sg::Operands o{skinny::check_x(x, op, 16), x.stride(0)};
+  auto y = sg::resolve(op, wq, wscale, bias, x.size(0), x.options(), o);
+  SXE_CHECK(x.size(1) == o.K, op, ": x [M, K], wq [N, K]");
+  sg::launch(sg::PRO_NONE, o, sg::ProArgs{}, y);
   return y;
 }
 
@@ -560,20 +576,14 @@ static std::vector<at::Tensor> skinny_gemm_pro_impl(const at::Tensor& x, const c
                                                     const at::Tensor& w, const c10::optional<at::Tensor>& wscale,
                                                     const c10::optional<at::Tensor>& bias, int64_t mode,
                                                     const RopeTensors* rope) {
-  SXE_CHECK_CUDA(x);
-  SXE_CHECK(mode == sg::PRO_RMS || mode == sg::PRO_SWIGLU, "skinny_gemm_pro: mode 1 (rms) or 2 (swiglu)");
-  SXE_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
-                reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0, "skinny_gemm_pro: x bf16 [M, *], 16-B rows");
-  const bool fp8 = wscale.has_value() && wscale->defined();
-  SXE_CHECK(w.dim() == 2 && w.stride(1) == 1 && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-            "skinny_gemm_pro: w [N, K] row-major, 16-B aligned");
-  SXE_CHECK(fp8 ? w.element_size() == 1 : w.scalar_type() == at::kBFloat16, "skinny_gemm_pro: w bf16 or fp8 bytes");
-  const int M = x.size(0), N = w.size(0), K = w.size(1);
-  SXE_CHECK(M >= 1 && M <= sg::kProMaxM, "skinny_gemm_pro: 1 <= M <= 4");
-  SXE_CHECK(x.size(1) == (mode == sg::PRO_SWIGLU ? 2 * K : K), "skinny_gemm_pro: x width");
-  SXE_CHECK(K % (fp8 ? 16 : 8) == 0 && w.stride(0) % (fp8 ? 16 : 8) == 0, "skinny_gemm_pro: K alignment");
+  constexpr const char* op = "skinny_gemm_pro";
+  SXE_CHECK(mode == sg::PRO_RMS || mode == sg::PRO_SWIGLU, op, ": mode 1 (rms) or 2 (swiglu)");
+  sg::Operands o{skinny::check_x(x, op, sg::kProMaxM), x.stride(0)};
+  auto y = sg::resolve(op, w, wscale, bias, x.size(0), x.options(), o);
+  const int M = o.M, K = o.K;
+  SXE_CHECK(x.size(1) == (mode == sg::PRO_SWIGLU ? 2 * K : K), op, ": x width");
+  o.lds = sg::act_bytes(o, op);
   sg::ProArgs pro{nullptr, nullptr, nullptr, (float)eps};
-  pro.nt = sg::nt_loads();
   if (rope != nullptr) {
     SXE_CHECK(mode == sg::PRO_RMS && !(bias.has_value() && bias->defined()), "skinny_gemm_pro_rope: RMS mode, no bias");
     const int64_t nq = rope->nq, nkv = rope->nkv;
@@ -610,66 +620,7 @@ static std::vector<at::Tensor> skinny_gemm_pro_impl(const at::Tensor& x, const c
       pro.hout = reinterpret_cast<unsigned short*>(h.data_ptr());
     }
   }
-  const unsigned short* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, "bias: bf16 [N]");
-    bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-  }
-  auto y = at::empty({M, N}, x.options());
-  if (N == 0) return {y, h.defined() ? h : x};
-  c10::DeviceGuard gd(x.device());
-  const size_t lds = (size_t)M * K * 2;
-  SXE_CHECK(lds <= 144 * 1024, "skinny_gemm_pro: M x K input exceeds the LDS budget");
-  const int tiles = (N + 15) / 16;
-  auto* xp = reinterpret_cast<const unsigned short*>(x.data_ptr());
-  auto* yp = reinterpret_cast<unsigned short*>(y.data_ptr());
-  static bool attr[3][2][2] = {};  // [bf16 / fp8 / bf16 nt][NW == 8][mode]
-  auto set = [&](const void* f, int a, int b, int c) {
-    if (!attr[a][b][c]) {
-      SXE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-      attr[a][b][c] = true;
-    }
-  };
-  const int mi = mode == sg::PRO_RMS ? 0 : 1;
-  if (!fp8) {
-    const int ss_total = (K + sg::kSS - 1) / sg::kSS;
-    int nw = 4, spw = 1;
-    sg::plan(tiles, ss_total, nw, spw);
-    auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-#define SXE_SGP1(NW, MODE, NT)                                                                                       \
-  do {                                                                                                               \
-    set(reinterpret_cast<const void*>(&sg::skinny_gemm_kernel<NW, MODE, NT>), NT ? 2 : 0, NW == 8, mi);              \
-    hipLaunchKernelGGL((sg::skinny_gemm_kernel<NW, MODE, NT>), dim3(tiles), dim3(NW * 64), lds, cur_stream(), xp,     \
-                       x.stride(0), wp, w.stride(0), bp, yp, y.stride(0), M, N, K, spw, pro);                         \
-  } while (0)
-#define SXE_SGP(NW, MODE)                                                                                            \
-  do {                                                                                                               \
-    if (pro.nt) SXE_SGP1(NW, MODE, true);                                                                            \
-    else SXE_SGP1(NW, MODE, false);                                                                                  \
-  } while (0)
-    if (mode == sg::PRO_RMS) { if (nw == 4) SXE_SGP(4, sg::PRO_RMS); else SXE_SGP(8, sg::PRO_RMS); }
-    else { if (nw == 4) SXE_SGP(4, sg::PRO_SWIGLU); else SXE_SGP(8, sg::PRO_SWIGLU); }
-#undef SXE_SGP
-#undef SXE_SGP1
-  } else {
-    SXE_CHECK(wscale->scalar_type() == at::kFloat && wscale->is_contiguous() && wscale->numel() == N,
-              "skinny_gemm_pro: wscale fp32 [N]");
-    const int ss_total = (K + sg::kSS8 - 1) / sg::kSS8;
-    const int nw = sg::pick_nw(tiles, ss_total, 2, 2);
-    const int spw = (ss_total + nw - 1) / nw;
-    auto* wp = reinterpret_cast<const uint8_t*>(w.data_ptr());
-    const float* sp = wscale->data_ptr<float>();
-#define SXE_SGP8(NW, MODE)                                                                                           \
-  do {                                                                                                               \
-    set(reinterpret_cast<const void*>(&sg::skinny_gemm_fp8w_kernel<NW, MODE>), 1, NW == 8, mi);                      \
-    hipLaunchKernelGGL((sg::skinny_gemm_fp8w_kernel<NW, MODE>), dim3(tiles), dim3(NW * 64), lds, cur_stream(), xp,    \
-                       x.stride(0), wp, w.stride(0), sp, bp, yp, y.stride(0), M, N, K, spw, pro);                     \
-  } while (0)
-    if (mode == sg::PRO_RMS) { if (nw == 4) SXE_SGP8(4, sg::PRO_RMS); else SXE_SGP8(8, sg::PRO_RMS); }
-    else { if (nw == 4) SXE_SGP8(4, sg::PRO_SWIGLU); else SXE_SGP8(8, sg::PRO_SWIGLU); }
-#undef SXE_SGP8
-  }
-  SXE_LAUNCH_CHECK();
+  sg::launch((int)mode, o, pro, y);
   return {y, h.defined() ? h : x};
 }
 
@@ -696,6 +647,7 @@ std::vector<at::Tensor> skinny_gemm_pro_rope(const at::Tensor& x, const c10::opt
 // (wscale None) or e4m3 bytes with wscale fp32 [N]; K = nq * D. One launch instead of merge + GEMM.
 at::Tensor skinny_gemm_merge(const at::Tensor& part_o, const at::Tensor& part_ml, const at::Tensor& w,
                              const c10::optional<at::Tensor>& wscale, const c10::optional<at::Tensor>& bias) {
+  constexpr const char* op = "skinny_gemm_merge";
   SXE_CHECK_CUDA(part_o);
   SXE_CHECK(part_o.scalar_type() == at::kFloat && part_o.dim() == 4 && part_o.is_contiguous() &&
                 part_ml.scalar_type() == at::kFloat && part_ml.is_contiguous() && part_ml.dim() == 4 &&
@@ -703,72 +655,15 @@ at::Tensor skinny_gemm_merge(const at::Tensor& part_o, const at::Tensor& part_ml
                 part_ml.size(2) == part_o.size(2) && part_ml.size(3) == 2,
             "skinny_gemm_merge: part_o fp32 [S, M, nq, D], part_ml fp32 [S, M, nq, 2]");
   const int S = part_o.size(0), M = part_o.size(1), nq = part_o.size(2), D = part_o.size(3);
-  const bool fp8 = wscale.has_value() && wscale->defined();
-  SXE_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.is_contiguous() && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-            "skinny_gemm_merge: w [N, K] row-major, 16-B aligned");
-  SXE_CHECK(fp8 ? w.element_size() == 1 : w.scalar_type() == at::kBFloat16, "skinny_gemm_merge: w bf16 or fp8 bytes");
-  const int N = w.size(0), K = w.size(1);
-  SXE_CHECK(K == nq * D && D % 8 == 0 && M >= 1 && M <= sg::kProMaxM && S >= 1, "skinny_gemm_merge: K = nq * D, M <= 4");
-  SXE_CHECK(K % (fp8 ? 16 : 8) == 0, "skinny_gemm_merge: K alignment");
+  SXE_CHECK(D % 8 == 0 && M >= 1 && M <= sg::kProMaxM && S >= 1 && w.is_contiguous(), op,
+            ": D a multiple of 8, M <= 4, w contiguous");
+  sg::Operands o{nullptr, 0};
+  auto y = sg::resolve(op, w, wscale, bias, M, part_o.options(), o);
+  SXE_CHECK(o.K == nq * D, op, ": K = nq * D");
+  o.ldx = o.K;
+  o.lds = sg::act_bytes(o, op);
   sg::ProArgs pro{nullptr, nullptr, nullptr, 0.f, part_o.data_ptr<float>(), part_ml.data_ptr<float>(), S, nq};
-  pro.nt = sg::nt_loads();
-  const unsigned short* bp = nullptr;
-  if (bias.has_value() && bias->defined()) {
-    SXE_CHECK(bias->scalar_type() == at::kBFloat16 && bias->is_contiguous() && bias->numel() == N, "bias: bf16 [N]");
-    bp = reinterpret_cast<const unsigned short*>(bias->data_ptr());
-  }
-  auto y = at::empty({M, N}, part_o.options().dtype(at::kBFloat16));
-  if (N == 0) return y;
-  c10::DeviceGuard gd(part_o.device());
-  const size_t lds = (size_t)M * K * 2;
-  SXE_CHECK(lds <= 144 * 1024, "skinny_gemm_merge: M x K input exceeds the LDS budget");
-  const int tiles = (N + 15) / 16;
-  auto* yp = reinterpret_cast<unsigned short*>(y.data_ptr());
-  static bool attr[3][2] = {};  // [bf16 / fp8 / bf16 nt][NW == 8]
-  auto set = [&](const void* f, int a, int b) {
-    if (!attr[a][b]) {
-      SXE_HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-      attr[a][b] = true;
-    }
-  };
-  if (!fp8) {
-    const int ss_total = (K + sg::kSS - 1) / sg::kSS;
-    int nw = 4, spw = 1;
-    sg::plan(tiles, ss_total, nw, spw);
-    auto* wp = reinterpret_cast<const unsigned short*>(w.data_ptr());
-#define SXE_SGM1(NW, NT)                                                                                             \
-  do {                                                                                                               \
-    set(reinterpret_cast<const void*>(&sg::skinny_gemm_kernel<NW, sg::PRO_MERGE, NT>), NT ? 2 : 0, NW == 8);         \
-    hipLaunchKernelGGL((sg::skinny_gemm_kernel<NW, sg::PRO_MERGE, NT>), dim3(tiles), dim3(NW * 64), lds,              \
-                       cur_stream(),                                                                                 \
-                       nullptr, K, wp, w.stride(0), bp, yp, y.stride(0), M, N, K, spw, pro);                          \
-  } while (0)
-#define SXE_SGM(NW)                                                                                                  \
-  do {                                                                                                               \
-    if (pro.nt) SXE_SGM1(NW, true);                                                                                  \
-    else SXE_SGM1(NW, false);                                                                                        \
-  } while (0)
-    if (nw == 4) SXE_SGM(4); else SXE_SGM(8);
-#undef SXE_SGM
-#undef SXE_SGM1
-  } else {
-    SXE_CHECK(wscale->scalar_type() == at::kFloat && wscale->is_contiguous() && wscale->numel() == N,
-              "skinny_gemm_merge: wscale fp32 [N]");
-    const int ss_total = (K + sg::kSS8 - 1) / sg::kSS8;
-    const int nw = sg::pick_nw(tiles, ss_total, 2, 2);
-    const int spw = (ss_total + nw - 1) / nw;
-    auto* wp = reinterpret_cast<const uint8_t*>(w.data_ptr());
-    const float* sp = wscale->data_ptr<float>();
-#define SXE_SGM8(NW)                                                                                                 \
-  do {                                                                                                               \
-    set(reinterpret_cast<const void*>(&sg::skinny_gemm_fp8w_kernel<NW, sg::PRO_MERGE>), 1, NW == 8);                 \
-    hipLaunchKernelGGL((sg::skinny_gemm_fp8w_kernel<NW, sg::PRO_MERGE>), dim3(tiles), dim3(NW * 64), lds,            \
-                       cur_stream(), nullptr, K, wp, w.stride(0), sp, bp, yp, y.stride(0), M, N, K, spw, pro);        \
-  } while (0)
-    if (nw == 4) SXE_SGM8(4); else SXE_SGM8(8);
-#undef SXE_SGM8
-  }
-  SXE_LAUNCH_CHECK();
+  sg::launch(sg::PRO_MERGE, o, pro, y);
   return y;
 }
 

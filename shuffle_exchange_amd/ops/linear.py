@@ -74,19 +74,25 @@ def _pro_ok(x, rows_max=4):
             and x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0 and not x.requires_grad)
 
 
-def fused_rms_linear(x, residual, norm_weight, eps, weight, bias=None):
-    """Decode (<= 4 rows): ``linear(rms_norm(x + residual), weight)`` in ONE launch
-    (skinny_gemm.hip PRO_RMS). Returns (y, h = x + residual) -- h is x itself without a residual --
-    or None when the fused kernel does not cover the operands (the caller runs the unfused ops)."""
+def _rms_operands(x, residual, norm_weight, weight):
+    """(w, scale) when the PRO_RMS kernels cover (x, residual, norm_weight, weight), else None."""
     wk = _pro_weight(weight)
     if wk is None or not _pro_ok(x) or norm_weight.dtype != torch.bfloat16 or not norm_weight.is_contiguous():
         return None
     if residual is not None and (residual.shape != x.shape or residual.stride() != x.stride()
                                  or residual.dtype != x.dtype):
         return None
-    w, sc = wk
-    if x.shape[1] != w.shape[1]:
+    return wk if x.shape[1] == wk[0].shape[1] else None
+
+
+def fused_rms_linear(x, residual, norm_weight, eps, weight, bias=None):
+    """Decode (<= 4 rows): ``linear(rms_norm(x + residual), weight)`` in ONE launch
+    (skinny_gemm.hip PRO_RMS). Returns (y, h = x + residual) -- h is x itself without a residual --
+    or None when the fused kernel does not cover the operands (the caller runs the unfused ops)."""
+    wk = _rms_operands(x, residual, norm_weight, weight)
+    if wk is None:
         return None
+    w, sc = wk
     y, h = torch.ops.sxe.skinny_gemm_pro(x, residual, norm_weight, float(eps), w, sc, bias, 1)
     return y, (h if residual is not None else x)
 
@@ -96,16 +102,11 @@ def fused_rms_rope_linear(x, residual, norm_weight, eps, weight, rope, positions
     RoPE + paged-KV-append epilogue (skinny_gemm.hip ``skinny_gemm_pro_rope``; head dim 128).
     Returns (qkv with q / k rotated, h) -- the rotated k and v are already in ``cache`` -- or None
     when not covered (the caller runs fused_rms_linear + rope_kv_cache_append)."""
-    wk = _pro_weight(weight)
-    if (wk is None or not _pro_ok(x) or norm_weight.dtype != torch.bfloat16 or not norm_weight.is_contiguous()
-            or rope.cos.shape[-1] != 64 or not cache.is_contiguous() or cache.dim() != 5 or cache.shape[-1] != 128):
-        return None
-    if residual is not None and (residual.shape != x.shape or residual.stride() != x.stride()
-                                 or residual.dtype != x.dtype):
+    wk = _rms_operands(x, residual, norm_weight, weight)
+    if (wk is None or rope.cos.shape[-1] != 64 or not cache.is_contiguous() or cache.dim() != 5
+            or cache.shape[-1] != 128 or wk[0].shape[0] != (nq + 2 * nkv) * 128):
         return None
     w, sc = wk
-    if x.shape[1] != w.shape[1] or w.shape[0] != (nq + 2 * nkv) * 128:
-        return None
     y, h = torch.ops.sxe.skinny_gemm_pro_rope(x, residual, norm_weight, float(eps), w, sc, rope.cos, rope.sin,
                                               positions.reshape(-1).contiguous().long(), slots, cache, int(nq), int(nkv))
     return y, (h if residual is not None else x)

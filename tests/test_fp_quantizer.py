@@ -132,7 +132,7 @@ def test_fpx_kernels_gpu(bits):
     torch.testing.assert_close(qg.get_scales().cpu(), qc.get_scales(), rtol=0, atol=0)
     assert torch.equal(codes_gpu.cpu(), codes_cpu)
     torch.testing.assert_close(qg.dequantize(codes_gpu).float().cpu(), qc.dequantize(codes_cpu).float(), rtol=0, atol=0)
-    for N, K in [(16, 128), (200, 4096), (1000, 1536)]:
+    for N, K in [(16, 128), (200, 4096), (1000, 1536), (40, 512), (40, 1024)]:  # K = 512 / 1024: 4 / 8 waves
         w = torch.randn(N, K) * 0.05
         fc, fg = FPxWeight(w, bits), FPxWeight(w.cuda().bfloat16(), bits)
         wd = FPxWeight(w.bfloat16(), bits).dequantize(torch.float32)

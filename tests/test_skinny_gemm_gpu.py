@@ -28,22 +28,27 @@ def test_skinny_gemm_matches_fp32(M, N, K, with_bias):
 
 
 @pytest.mark.parametrize("M", [1, 4])
-@pytest.mark.parametrize("N,K", [(100, 264), (4104, 4096)])
+@pytest.mark.parametrize("N,K", [(100, 264), (4104, 4096), (40, 4096), (40, 8448)])
 def test_skinny_gemm_nontemporal_loads_match(M, N, K, monkeypatch):
     """SXE_SKINNY_NT=1 (non-temporal weight loads: separate kernel instantiations) gives the same
-    bits as the default loads, for the plain GEMM and the fused RMSNorm / SwiGLU prologues."""
+    bits as the default loads, for the plain GEMM and the fused RMSNorm / SwiGLU / merge prologues.
+    N = 40 at K >= 4096 takes the 8-wave kernels; M = 4 at K = 8448 needs more than 64 KiB of LDS."""
     g = torch.Generator(device="cuda").manual_seed(N + K)
     x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16, generator=g)
     w = torch.randn(N, K, device="cuda", dtype=torch.bfloat16, generator=g)
     gw = torch.rand(K, device="cuda", generator=g).bfloat16()
     x2 = torch.randn(M, 2 * K, device="cuda", dtype=torch.bfloat16, generator=g)
+    D = 128 if K % 128 == 0 else 8
+    po = torch.randn(2, M, K // D, D, device="cuda", generator=g)
+    pml = torch.rand(2, M, K // D, 2, device="cuda", generator=g) + 0.5
     outs = []
     for nt in ("0", "1"):
         monkeypatch.setenv("SXE_SKINNY_NT", nt)
         y = torch.ops.sxe.skinny_gemm(x, w, None)
         yr = torch.ops.sxe.skinny_gemm_pro(x, None, gw, 1e-5, w, None, None, 1)[0]
         ys = torch.ops.sxe.skinny_gemm_pro(x2, None, None, 0.0, w, None, None, 2)[0]
-        outs.append((y, yr, ys))
+        ym = torch.ops.sxe.skinny_gemm_merge(po, pml, w, None, None)
+        outs.append((y, yr, ys, ym))
     for a, b in zip(*outs):
         assert torch.equal(a, b)
 
@@ -98,12 +103,13 @@ def test_hf_engine_quantized_weights_close_to_bf16(kind, min_cos):
 
 
 @pytest.mark.parametrize("M", [1, 3, 4])
-@pytest.mark.parametrize("K,N", [(4096, 6144), (4096, 28672), (512, 200)])
+@pytest.mark.parametrize("K,N", [(4096, 6144), (4096, 28672), (512, 200), (4096, 40), (8448, 40)])
 @pytest.mark.parametrize("fp8", [False, True])
 @pytest.mark.parametrize("with_res", [True, False])
 def test_fused_rms_prologue_vs_fp32(M, K, N, fp8, with_res):
     """skinny_gemm_pro mode 1: residual add + RMSNorm + GEMM in one launch == the fp32 reference of
-    the separate ops (h rounded to bf16 like the norm kernel), and h = x + res written out."""
+    the separate ops (h rounded to bf16 like the norm kernel), and h = x + res written out.
+    N = 40 at K >= 4096 takes the 8-wave kernels; M = 4 at K = 8448 needs more than 64 KiB of LDS."""
     from shuffle_exchange_amd.ops.fp_quantizer import FP8Weight
     from shuffle_exchange_amd.ops.linear import fused_rms_linear
     torch.manual_seed(0)
@@ -170,13 +176,14 @@ def test_decode_fused_layer_matches_unfused(monkeypatch):
     assert err < 2e-2, err
 
 
-@pytest.mark.parametrize("M", [1, 3])
+@pytest.mark.parametrize("M", [1, 3, 4])
 @pytest.mark.parametrize("splits", [2, 16, 37])
-@pytest.mark.parametrize("nq,D,N", [(32, 128, 4096), (8, 64, 200)])
+@pytest.mark.parametrize("nq,D,N", [(32, 128, 4096), (8, 64, 200), (66, 128, 40)])
 @pytest.mark.parametrize("fp8", [False, True])
 def test_fused_merge_prologue_vs_fp32(M, splits, nq, D, N, fp8):
     """skinny_gemm_merge: the flash-decoding merge of KV-split partials (some splits empty: max -inf)
-    as the o_proj GEMM's prologue == the fp32 merge followed by the GEMM."""
+    as the o_proj GEMM's prologue == the fp32 merge followed by the GEMM. (66, 128, 40) is K = 8448
+    on the 8-wave kernels, more than 64 KiB of LDS at M = 4."""
     from shuffle_exchange_amd.ops.fp_quantizer import FP8Weight
     from shuffle_exchange_amd.ops.linear import fused_merge_linear
     torch.manual_seed(2)
@@ -240,9 +247,10 @@ def test_decode_merge_fused_o_proj_matches_unfused(monkeypatch):
 
 
 @pytest.mark.parametrize("M", [1, 3])
-@pytest.mark.parametrize("nq,nkv", [(32, 8), (4, 2)])
+@pytest.mark.parametrize("K,nq,nkv", [pytest.param(1024, 32, 8, id="32-8"), pytest.param(1024, 4, 2, id="4-2"),
+                                      pytest.param(4096, 4, 2, id="K4096-4-2")])  # K = 4096: the 8-wave kernels
 @pytest.mark.parametrize("fp8", [False, True])
-def test_fused_rms_rope_epilogue_vs_separate_ops(M, nq, nkv, fp8):
+def test_fused_rms_rope_epilogue_vs_separate_ops(M, K, nq, nkv, fp8):
     """skinny_gemm_pro_rope (RMSNorm prologue + QKV GEMM + RoPE / KV-append epilogue) == the fused
     RMS GEMM followed by rope_kv_cache_append (rotation from the fp32 accumulator instead of the
     bf16-rounded output: within bf16 rounding); slots of -1 leave the cache untouched."""
@@ -251,12 +259,13 @@ def test_fused_rms_rope_epilogue_vs_separate_ops(M, nq, nkv, fp8):
     from shuffle_exchange_amd.ops.paged_attention import rope_kv_cache_append
     from shuffle_exchange_amd.ops.rope import RopeCache
     torch.manual_seed(3)
-    K, D, bs, nblk = 1024, 128, 16, 8
+    D, bs, nblk = 128, 16, 8
     N = (nq + 2 * nkv) * D
     x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
     res = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
     g = (1.0 + 0.1 * torch.randn(K, device="cuda")).to(torch.bfloat16)
-    w = (0.05 * torch.randn(N, K, device="cuda")).to(torch.bfloat16)
+    # 0.05 at K = 1024; scaled so that the outputs, whose bf16 rounding atol covers, do not grow with K
+    w = (0.05 * (1024 / K) ** 0.5 * torch.randn(N, K, device="cuda")).to(torch.bfloat16)
     wobj = FP8Weight(w) if fp8 else w
     rope = RopeCache(D, 4096, 500000.0, device="cuda")
     pos = torch.randint(0, 4096, (M,), device="cuda")
