@@ -143,6 +143,24 @@ __device__ __forceinline__ int build_tile_list(const Sparse sp, int head, int t_
   return list[-1];
 }
 
+// Band mask (packed documents and / or a sliding window, on top of the causal mask): query i sees keys
+// klo[i] <= j <= i, equivalently key j is seen by queries j <= i <= qhi[j]. Both int32 [B, S], non-decreasing
+// along S (a precondition of the raw ops, not checked on the device: a workgroup takes its first K/V tile
+// from the klo of its first row and the end of its query sweep from the qhi of its last key). Every
+// value is clamped on read -- klo to [0, i], qhi to [j, S - 1] -- and every tile index derives from the
+// clamped values, so wrong bounds give wrong numbers but never an out-of-range tile or address.
+// Band mode needs causal, Sq == Sk, causal offset 0 and a dense layout (checked on the host).
+struct Band {
+  const int* klo;  // nullptr = no band
+  const int* qhi;
+};
+__device__ __forceinline__ int band_klo(const Band& bd, int b, int S, int i) {
+  return min(max(bd.klo[(int64_t)b * S + i], 0), i);
+}
+__device__ __forceinline__ int band_qhi(const Band& bd, int b, int S, int j) {
+  return max(min(bd.qhi[(int64_t)b * S + j], S - 1), j);
+}
+
 // Heavy-first mapping of the flat block index onto (b, head, row-block) for the causal triangle.
 __device__ __forceinline__ void map_block(int nblk, int BH, bool heavy_last_index, int& bh, int& blk) {
   const int idx = blockIdx.x;
@@ -190,15 +208,16 @@ __device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t ro
 // One K/V tile of a wave's online softmax. MASK = false is the interior-tile body (no causal
 // diagonal, no padded tail, dense): none of the per-score compares / selects are emitted -- on
 // the Llama-3 shape ~90 % of the tiles take it; the masked body handles the diagonal, the kv_len
-// tail and block-sparse layouts.
-template <bool MASK, int D>
+// tail and block-sparse layouts. BAND (band kernels only): `band` says the tile holds keys below the
+// klo of some row of the wave; `kl` is this lane's (clamped) klo.
+template <bool MASK, int D, bool BAND = false>
 __device__ __forceinline__ void fwd_tile(const LaneOffs<D>& lo, const char* kt, const char* vt, const bf16x8 (&qf)[D / 16],
                                          f32x16 (&oacc)[D / 32], float& m, float& l, float c, int kbase, int qpos,
                                          int r, int h, int lane, bool diag, bool tail, int kvlen, const uint8_t* lrow,
-                                         int blk) {
+                                         int blk, bool band = false, int kl = 0) {
   // causal diagonal tile whose second 32-key half lies entirely above this wave's last query
   // (the wave's queries start at the tile's first key): that half's QK^T and PV MFMAs are skipped
-  const bool skip1 = MASK && diag && !tail && lrow == nullptr && kbase + 32 > qpos + QW - 1;
+  const bool skip1 = MASK && diag && !tail && lrow == nullptr && !(BAND && band) && kbase + 32 > qpos + QW - 1;
   f32x16 s[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -213,6 +232,8 @@ __device__ __forceinline__ void fwd_tile(const LaneOffs<D>& lo, const char* kt, 
   // compile-time row constants instead of 32 hoisted per-row thresholds per mask (VGPRs)
   int dd = kbase + 4 * h - qpos - r, dl = kbase + 4 * h - kvlen;
   if (MASK) asm volatile("" : "+v"(dd), "+v"(dl));
+  int db = kbase + 4 * h - kl;  // key - klo of this lane's first score row
+  if (BAND) asm volatile("" : "+v"(db));
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     bool b0 = true, b1 = true;  // layout bits of keys kbase+32j+[0,16) and +[16,32)
@@ -227,6 +248,7 @@ __device__ __forceinline__ void fwd_tile(const LaneOffs<D>& lo, const char* kt, 
         if (diag && dd + 32 * j + acc_row(i, 0) > 0) x = -INFINITY;
         if (tail && dl + 32 * j + acc_row(i, 0) >= 0) x = -INFINITY;
         if (!(i < 8 ? b0 : b1)) x = -INFINITY;
+        if (BAND && band && db + 32 * j + acc_row(i, 0) < 0) x = -INFINITY;
         s[j][i] = x;
       }
       mx = fmaxf(mx, x);
@@ -282,13 +304,15 @@ constexpr int fwd_min_waves() { return D >= 256 ? 1 : 8 / NWF; }
 // accumulator + 64 Q-fragment registers), smaller head dims by default (SXE_FA_FWD_DMA=0 selects the
 // register Stager: 4-7 % slower at D 128, B4 S2048 to B1 S32k, equal at D 64 --
 // profiles/r05/attn_fwd_dma_ab.log)
-template <bool SPARSE, int NWF, int D, bool DMA = (D >= 256)>
-__global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_kernel(
+// The body is shared by fwd_kernel (dense / sparse) and fwd_band_kernel (BAND: the tile walk starts at
+// the first tile the workgroup's first row sees, a wave skips the tiles wholly below its first row's
+// klo, and tiles that the klo of its last row cuts take the masked body with one more compare).
+template <bool SPARSE, int NWF, int D, bool DMA, bool BAND>
+__device__ __forceinline__ void fwd_body(
     const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
     const unsigned short* __restrict__ v, Strides vs, unsigned short* __restrict__ o, Strides os,
     float* __restrict__ lse, int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen,
-    int qoff) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+    int qoff, Band bd) {
   constexpr int ROWB = 2 * D;
   constexpr int BUF = 2 * KT * ROWB;  // one ring slot = K tile + V tile
   int* tlist = reinterpret_cast<int*>(smem + 4 * KT * ROWB) + 1;
@@ -319,8 +343,14 @@ __global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_kerne
   // keys needed by the workgroup (causal: up to its last query's diagonal)
   const int kend = causal ? min(Sk, (qb + 1) * QBF + qoff) : Sk;
   const int nkt = (max(kend, 0) + KT - 1) / KT;
-  const int ntiles = SPARSE ? build_tile_list(sp, head, 0, nkt, KT, qb * QBF, qb * QBF + QBF, true, tlist) : nkt;
-  auto tile_at = [&](int i) { return SPARSE ? tlist[i] : i; };
+  // band: first tile of the workgroup, this lane's klo and the klo of the wave's first / last row
+  const int tfirst = BAND ? band_klo(bd, b, Sq, qb * QBF) / KT : 0;
+  const int kl = BAND ? band_klo(bd, b, Sq, q0 + r) : 0;
+  const int kl_lo = BAND ? __builtin_amdgcn_readfirstlane(kl) : 0;
+  const int kl_hi = BAND ? __builtin_amdgcn_readlane(kl, QW - 1) : 0;
+  const int ntiles = SPARSE ? build_tile_list(sp, head, 0, nkt, KT, qb * QBF, qb * QBF + QBF, true, tlist)
+                            : (BAND ? nkt - tfirst : nkt);
+  auto tile_at = [&](int i) { return SPARSE ? tlist[i] : (BAND ? tfirst + i : i); };
   const uint8_t* lrow = SPARSE ? sp.layout + ((int64_t)head * sp.nb + (q0 + r) / sp.blk) * sp.nb : nullptr;
   Stager<KT, NWF, D> sk, sv;
   const int t0 = ntiles > 0 ? tile_at(0) : 0;
@@ -356,15 +386,16 @@ __global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_kerne
     }
     const int kbase = tile_at(t) * KT;
     // a wave whose queries all precede this tile has nothing to add (causal)
-    const bool active = !causal || kbase <= qpos + QW - 1;
+    const bool active = (!causal || kbase <= qpos + QW - 1) && !(BAND && kbase + KT - 1 < kl_lo);
     if (active) {
       const char* kt = smem + CUR * BUF;
       const char* vt = kt + KT * ROWB;
       const bool diag = causal && (kbase + KT - 1 > qpos);
       const bool tail = kbase + KT > kvlen;  // keys past the valid length (padded key axis)
-      if (SPARSE || diag || tail)
-        fwd_tile<true, D>(lo, kt, vt, qf, oacc, m, l, c, kbase, qpos, r, h, lane, diag, tail, kvlen, lrow,
-                          SPARSE ? sp.blk : 1);
+      const bool band = BAND && kbase < kl_hi;
+      if (SPARSE || diag || tail || band)
+        fwd_tile<true, D, BAND>(lo, kt, vt, qf, oacc, m, l, c, kbase, qpos, r, h, lane, diag, tail, kvlen, lrow,
+                                SPARSE ? sp.blk : 1, band, kl);
       else
         fwd_tile<false, D>(lo, kt, vt, qf, oacc, m, l, c, kbase, qpos, r, h, lane, false, false, kvlen, nullptr, 1);
     }
@@ -393,6 +424,27 @@ __global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_kerne
       *reinterpret_cast<u16x4*>(op + 32 * dt + 8 * rg + 4 * h) = pk;
     }
   if (h == 0) lse[((int64_t)b * H + head) * Sq + q0 + r] = lt > 0.f ? (m + log2f(lt)) * LN2 : INFINITY;
+}
+
+template <bool SPARSE, int NWF, int D, bool DMA = (D >= 256)>
+__global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, unsigned short* __restrict__ o, Strides os,
+    float* __restrict__ lse, int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen,
+    int qoff) {
+  fwd_body<SPARSE, NWF, D, DMA, false>(q, qs, k, ks, v, vs, o, os, lse, B, H, Hk, Sq, Sk, scale, causal, sp, kvlen,
+                                       qoff, Band{nullptr, nullptr});
+}
+
+// Band mode always stages K/V by LDS-DMA (SXE_FA_FWD_DMA=0 is ignored here: one forward variant per
+// head dim and wave count keeps the compile time down, and the DMA form is the faster one).
+template <int NWF, int D>
+__global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_band_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, unsigned short* __restrict__ o, Strides os,
+    float* __restrict__ lse, int B, int H, int Hk, int S, float scale, Band bd) {
+  fwd_body<false, NWF, D, true, true>(q, qs, k, ks, v, vs, o, os, lse, B, H, Hk, S, S, scale, 1,
+                                      Sparse{nullptr, 0, 0}, S, 0, bd);
 }
 
 // =============================================================================================
@@ -433,14 +485,18 @@ constexpr int bwd_min_waves() { return D >= 256 ? 1 : 2; }
 // dQ: forward-shaped. Per wave 32 queries; per K/V tile recompute S^T, P^T, dP^T = V dO^T,
 // dS^T = P^T (dP^T - delta), dQ^T += K^T dS^T.
 // =============================================================================================
-template <bool MASK, int D>
+template <bool MASK, int D, bool BAND = false>
 __device__ __forceinline__ void dq_tile(const LaneOffs<D>& lo, const char* kt, const char* vt, const bf16x8 (&qf)[D / 16],
                                         const bf16x8 (&df)[D / 16], f32x16 (&dqacc)[D / 32], float c, float lse2,
                                         float ndlt, int kbase, int qpos, int r, int h, int lane, bool diag, bool tail,
-                                        int kvlen, const uint8_t* lay_row, int blk) {
+                                        int kvlen, const uint8_t* lay_row, int blk, bool band = false,
+                                        int kl = 0) {
   int dd = kbase + 4 * h - qpos - r, dl = kbase + 4 * h - kvlen;  // see fwd_tile
   if (MASK) asm volatile("" : "+v"(dd), "+v"(dl));
-  const bool skip1 = MASK && diag && !tail && lay_row == nullptr && kbase + 32 > qpos + QW - 1;  // see fwd_tile
+  int db = kbase + 4 * h - kl;  // band: key - klo, see fwd_tile
+  if (BAND) asm volatile("" : "+v"(db));
+  const bool skip1 = MASK && diag && !tail && lay_row == nullptr && !(BAND && band) &&
+                     kbase + 32 > qpos + QW - 1;  // see fwd_tile
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     if (j == 1 && skip1) break;
@@ -462,6 +518,7 @@ __device__ __forceinline__ void dq_tile(const LaneOffs<D>& lo, const char* kt, c
         if (diag && dd + 32 * j + acc_row(i, 0) > 0) p = 0.f;
         if (tail && dl + 32 * j + acc_row(i, 0) >= 0) p = 0.f;
         if (!(i < 8 ? b0 : b1)) p = 0.f;
+        if (BAND && band && db + 32 * j + acc_row(i, 0) < 0) p = 0.f;
       }
       s[i] = p * (dp[i] + ndlt);  // dS^T (ndlt = -delta)
     }
@@ -478,13 +535,13 @@ __device__ __forceinline__ void dq_tile(const LaneOffs<D>& lo, const char* kt, c
 // NWF waves per workgroup, 32 queries each: 8 (256 queries) shares every staged K/V tile among twice
 // the queries of 4 -- half the L2-to-LDS tile traffic per query, at one workgroup per CU
 // (SXE_FA_DQ_WAVES, read per call; Sq a multiple of 256, head dims 64 / 128)
-template <bool SPARSE, int D, int NWF = 4>
-__global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>())) dq_kernel(
+// (body shared with dq_band_kernel: BAND walks and masks the tiles as the forward does)
+template <bool SPARSE, int D, int NWF, bool BAND>
+__device__ __forceinline__ void dq_body(
     const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
     const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
     const float* __restrict__ lse, const float* __restrict__ ndelta, unsigned short* __restrict__ dq, Strides dqs,
-    int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen, int qoff) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+    int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen, int qoff, Band bd) {
   constexpr int ROWB = 2 * D;
   constexpr int BUF = 2 * KT * ROWB;
   int* tlist = reinterpret_cast<int*>(smem + 4 * KT * ROWB) + 1;
@@ -505,8 +562,13 @@ __global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>()))
   const int64_t lrow = ((int64_t)b * H + head) * Sq + q0 + r;
   const int kend = causal ? min(Sk, (qb + 1) * QBF + qoff) : Sk;
   const int nkt = (max(kend, 0) + KT - 1) / KT;
-  const int ntiles = SPARSE ? build_tile_list(sp, head, 0, nkt, KT, qb * QBF, qb * QBF + QBF, true, tlist) : nkt;
-  auto tile_at = [&](int i) { return SPARSE ? tlist[i] : i; };
+  const int tfirst = BAND ? band_klo(bd, b, Sq, qb * QBF) / KT : 0;  // band: see fwd_body
+  const int kl = BAND ? band_klo(bd, b, Sq, q0 + r) : 0;
+  const int kl_lo = BAND ? __builtin_amdgcn_readfirstlane(kl) : 0;
+  const int kl_hi = BAND ? __builtin_amdgcn_readlane(kl, QW - 1) : 0;
+  const int ntiles = SPARSE ? build_tile_list(sp, head, 0, nkt, KT, qb * QBF, qb * QBF + QBF, true, tlist)
+                            : (BAND ? nkt - tfirst : nkt);
+  auto tile_at = [&](int i) { return SPARSE ? tlist[i] : (BAND ? tfirst + i : i); };
   const uint8_t* lay_row = SPARSE ? sp.layout + ((int64_t)head * sp.nb + (q0 + r) / sp.blk) * sp.nb : nullptr;
   if (ntiles > 0) {
     tile_glds<KT, D, NWF>(kp, ks.s, tile_at(0) * KT, smem);
@@ -540,15 +602,16 @@ __global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>()))
       tile_glds<KT, D, NWF>(vp, vs.s, tile_at(t + 1) * KT, smem + (CUR ^ 1) * BUF + KT * ROWB);
     }
     const int kbase = tile_at(t) * KT;
-    const bool active = !causal || kbase <= qpos + QW - 1;
+    const bool active = (!causal || kbase <= qpos + QW - 1) && !(BAND && kbase + KT - 1 < kl_lo);
     if (active) {
       const char* kt = smem + CUR * BUF;
       const char* vt = smem + CUR * BUF + KT * ROWB;
       const bool diag = causal && (kbase + KT - 1 > qpos);
       const bool tail = kbase + KT > kvlen;
-      if (SPARSE || diag || tail)
-        dq_tile<true, D>(lo, kt, vt, qf, df, dqacc, c, lse2, ndlt, kbase, qpos, r, h, lane, diag, tail, kvlen,
-                         lay_row, SPARSE ? sp.blk : 1);
+      const bool band = BAND && kbase < kl_hi;
+      if (SPARSE || diag || tail || band)
+        dq_tile<true, D, BAND>(lo, kt, vt, qf, df, dqacc, c, lse2, ndlt, kbase, qpos, r, h, lane, diag, tail, kvlen,
+                               lay_row, SPARSE ? sp.blk : 1, band, kl);
       else
         dq_tile<false, D>(lo, kt, vt, qf, df, dqacc, c, lse2, ndlt, kbase, qpos, r, h, lane, false, false, kvlen,
                           nullptr, 1);
@@ -572,6 +635,26 @@ __global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>()))
     }
 }
 
+template <bool SPARSE, int D, int NWF = 4>
+__global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>())) dq_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
+    const float* __restrict__ lse, const float* __restrict__ ndelta, unsigned short* __restrict__ dq, Strides dqs,
+    int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen, int qoff) {
+  dq_body<SPARSE, D, NWF, false>(q, qs, k, ks, v, vs, dout, dos, lse, ndelta, dq, dqs, B, H, Hk, Sq, Sk, scale,
+                                 causal, sp, kvlen, qoff, Band{nullptr, nullptr});
+}
+
+template <int D, int NWF = 4>
+__global__ void __launch_bounds__(NWF * 64, (NWF == 8 ? 1 : bwd_min_waves<D>())) dq_band_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
+    const float* __restrict__ lse, const float* __restrict__ ndelta, unsigned short* __restrict__ dq, Strides dqs,
+    int B, int H, int Hk, int S, float scale, Band bd) {
+  dq_body<false, D, NWF, true>(q, qs, k, ks, v, vs, dout, dos, lse, ndelta, dq, dqs, B, H, Hk, S, S, scale, 1,
+                               Sparse{nullptr, 0, 0}, S, 0, bd);
+}
+
 // =============================================================================================
 // dK, dV: per wave 32 keys held on the lanes; sweep every query head of the GQA group and every
 // 32-query tile at or after the keys (causal). Q/dO tiles + LSE/delta arrive by LDS-DMA into a
@@ -588,12 +671,14 @@ template <int D, int KB = QB> struct KVL {
 
 // PART: 3 = dK and dV in one sweep; 1 = dV only; 2 = dK only (head dim 256: the two 128-register
 // accumulators of one sweep would spill, so two sweeps each recompute S = Q K^T)
-template <bool MASK, int D, int PART>
+// BAND (band kernels only): `band` says the tile holds queries above the qhi of some key of the
+// wave; `qh` is this lane's (clamped) qhi.
+template <bool MASK, int D, int PART, bool BAND = false>
 __device__ __forceinline__ void dkdv_tile(const LaneOffs<D>& lo, const char* slot, const char* vblk,
                                           const bf16x8 (&kf)[D / 16],
                                           f32x16 (&dka)[D / 32], f32x16 (&dva)[D / 32], float c, int qt0, int k0,
                                           int w, int r, int h, int lane, bool diag, const Sparse& sp, int hq0,
-                                          int kbl, int qoff) {
+                                          int kbl, int qoff, bool band = false, int qh = 0) {
   const char* qt = slot;
   const char* dt_ = slot + KVL<D>::TILE;
   const float* l2 = reinterpret_cast<const float*>(slot + 2 * KVL<D>::TILE);
@@ -626,6 +711,13 @@ __device__ __forceinline__ void dkdv_tile(const LaneOffs<D>& lo, const char* slo
     for (int i = 0; i < 16; ++i)
       if (!(acc_row(i, h) < 16 ? b0 : b1)) s[i] = 0.f;
   }
+  if (BAND && band) {
+    int db = qh - qt0 - 4 * h;  // masked iff query > qhi of this lane's key, i.e. row(i, 0) > db
+    asm volatile("" : "+v"(db));
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+      if (acc_row(i, 0) > db) s[i] = 0.f;
+  }
 #pragma unroll
   for (int i = 0; i < 16; ++i) dp[i] = s[i] * (dp[i] + dl[acc_row(i, h)]);  // dS = P (dP - delta); dl = -delta
 #pragma unroll
@@ -649,14 +741,16 @@ __device__ __forceinline__ void dkdv_tile(const LaneOffs<D>& lo, const char* slo
 // NWK waves per workgroup, 32 keys each: 8 (256 keys, head dim 128; SXE_FA_DKDV_WAVES, read per
 // call) shares every staged Q / dO tile among twice the keys of 4 -- half the L2-to-LDS traffic per
 // key, at one workgroup per CU
-template <bool SPLIT, int D, int PART = 3, int NWK = 4>
-__global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>())) dkdv_kernel(
+// The body is shared with dkdv_band_kernel (BAND: the query sweep of each head ends at the qhi of the
+// workgroup's last key, rounded up to the query tile; a wave skips the tiles wholly above its last
+// key's qhi, and tiles that the qhi of its first key cuts get one more mask).
+template <bool SPLIT, int D, int PART, int NWK, bool BAND>
+__device__ __forceinline__ void dkdv_body(
     const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
     const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
     const float* __restrict__ lse, const float* __restrict__ delta, unsigned short* __restrict__ dk, Strides dks,
     unsigned short* __restrict__ dv, Strides dvs, float* __restrict__ pk, float* __restrict__ pv, int B, int H,
-    int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int qoff, int hpw) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
+    int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int qoff, int hpw, Band bd) {
   constexpr int KB = NWK * QW;  // keys per workgroup
   using G_ = KVL<D, KB>;
   char* vblk = smem;
@@ -680,7 +774,13 @@ __global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>()))
   const float c = scale * LOG2E;
   // causal: the first query that sees key block kb (query i sees keys <= i + qoff)
   const int qstart = causal ? min(Sq, max(0, kb * KB - qoff) / QT * QT) : 0;
-  const int ntq = (Sq - qstart) / QT;
+  // end of the query sweep (band: past the last query that sees the workgroup's last key; <= Sq, a
+  // multiple of QT), this lane's qhi and the qhi of the wave's first / last key
+  const int qend = BAND ? (band_qhi(bd, b, Sq, kb * KB + KB - 1) / QT + 1) * QT : Sq;
+  const int qh = BAND ? band_qhi(bd, b, Sq, k0 + r) : 0;
+  const int qh_lo = BAND ? __builtin_amdgcn_readfirstlane(qh) : 0;
+  const int qh_hi = BAND ? __builtin_amdgcn_readlane(qh, QW - 1) : 0;
+  const int ntq = (qend - qstart) / QT;
   // sparse: SPLIT mode (G == 1), list of the active 32-query tiles of this key block
   const int total = sp.layout ? build_tile_list(sp, hq0, qstart / QT, Sq / QT, QT, kb * KB, kb * KB + KB, false, tlist)
                               : ntq * G;
@@ -695,7 +795,7 @@ __global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>()))
     const int qt0 = sp.layout ? tlist[it] * QT : is_q;
     if (!sp.layout) {
       is_q += QT;
-      if (is_q >= Sq) {
+      if (is_q >= qend) {
         is_q = qstart;
         ++is_h;
       }
@@ -732,13 +832,14 @@ __global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>()))
   auto step = [&](const int it, auto slotc) {
     constexpr int CUR = decltype(slotc)::value;
     const int qt0 = sp.layout ? tlist[it] * QT : c_q;
-    c_q = c_q + QT >= Sq ? qstart : c_q + QT;
-    const bool active = !causal || (qt0 + QT - 1 + qoff >= k0);
+    c_q = c_q + QT >= qend ? qstart : c_q + QT;
+    const bool active = (!causal || (qt0 + QT - 1 + qoff >= k0)) && !(BAND && qt0 > qh_hi);
     const bool diag = causal && (qt0 + qoff < k0 + QW);
+    const bool band = BAND && qt0 + QT - 1 > qh_lo;
     if (it + 1 < total) issue(it + 1, ring + (CUR ^ 1) * G_::SLOT);
     if (active)
-      dkdv_tile<true, D, PART>(lo, ring + CUR * G_::SLOT, vblk, kf, dka, dva, c, qt0, k0, w, r, h, lane, diag, sp,
-                               hq0, kbl, qoff);
+      dkdv_tile<true, D, PART, BAND>(lo, ring + CUR * G_::SLOT, vblk, kf, dka, dva, c, qt0, k0, w, r, h, lane, diag,
+                                     sp, hq0, kbl, qoff, band, qh);
     vm_wait_all();
     __syncthreads();
   };
@@ -779,6 +880,28 @@ __global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>()))
       if constexpr ((PART & 2) != 0) *reinterpret_cast<u16x4*>(kop + 32 * t + 8 * rg + 4 * h) = pk4;
       if constexpr ((PART & 1) != 0) *reinterpret_cast<u16x4*>(vop + 32 * t + 8 * rg + 4 * h) = pv4;
     }
+}
+
+template <bool SPLIT, int D, int PART = 3, int NWK = 4>
+__global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>())) dkdv_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
+    const float* __restrict__ lse, const float* __restrict__ delta, unsigned short* __restrict__ dk, Strides dks,
+    unsigned short* __restrict__ dv, Strides dvs, float* __restrict__ pk, float* __restrict__ pv, int B, int H,
+    int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int qoff, int hpw) {
+  dkdv_body<SPLIT, D, PART, NWK, false>(q, qs, k, ks, v, vs, dout, dos, lse, delta, dk, dks, dv, dvs, pk, pv, B, H,
+                                        Hk, Sq, Sk, scale, causal, sp, qoff, hpw, Band{nullptr, nullptr});
+}
+
+template <bool SPLIT, int D, int PART = 3, int NWK = 4>
+__global__ void __launch_bounds__(NWK * 64, (NWK == 8 ? 1 : bwd_min_waves<D>())) dkdv_band_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, const unsigned short* __restrict__ dout, Strides dos,
+    const float* __restrict__ lse, const float* __restrict__ delta, unsigned short* __restrict__ dk, Strides dks,
+    unsigned short* __restrict__ dv, Strides dvs, float* __restrict__ pk, float* __restrict__ pv, int B, int H,
+    int Hk, int S, float scale, int hpw, Band bd) {
+  dkdv_body<SPLIT, D, PART, NWK, true>(q, qs, k, ks, v, vs, dout, dos, lse, delta, dk, dks, dv, dvs, pk, pv, B, H,
+                                       Hk, S, S, scale, 1, Sparse{nullptr, 0, 0}, 0, hpw, bd);
 }
 
 
@@ -846,6 +969,16 @@ static fa::Sparse sparse_of(const c10::optional<at::Tensor>& layout, int64_t blo
   return fa::Sparse{L.data_ptr<uint8_t>(), (int)block, (int)(S / block)};
 }
 
+// klo / qhi of band mode: int32 [B, S] contiguous on q's device (values are clamped by the kernels)
+static fa::Band band_of(const at::Tensor& klo, const at::Tensor& qhi, const at::Tensor& q, const at::Tensor& k) {
+  SXE_CHECK(q.dim() == 4 && k.dim() == 4 && q.size(1) == k.size(1), "flash_attn band: needs Sq == Sk");
+  for (const at::Tensor* t : {&klo, &qhi})
+    SXE_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                  t->dim() == 2 && t->size(0) == q.size(0) && t->size(1) == q.size(1),
+              "flash_attn band: klo / qhi must be contiguous int32 [B, S] on the device of q");
+  return fa::Band{klo.data_ptr<int>(), qhi.data_ptr<int>()};
+}
+
 constexpr size_t kListBytes = (1 + 2048) * sizeof(int) + 16;  // tile list + scratch flags (sparse mode)
 
 // Kernel-variant knob, read on every call (not cached at static init) so a test or an A/B run can
@@ -874,7 +1007,7 @@ static void set_lds_limit(F* f, size_t bytes) {
 // keys <= i + qoff), default Sk - Sq (bottom-right aligned)
 template <int D>
 static std::vector<at::Tensor> fwd_impl_d(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
-                                          fa::Sparse sp, int kvlen, int qoff) {
+                                          fa::Sparse sp, int kvlen, int qoff, fa::Band bd) {
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1), Hk = k.size(2);
   auto o = at::empty({B, Sq, H, D}, q.options());
   auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
@@ -892,7 +1025,9 @@ static std::vector<at::Tensor> fwd_impl_d(at::Tensor q, at::Tensor k, at::Tensor
       set_lds_limit(&fa::fwd_kernel<true, 4, D, true>, mx);
       set_lds_limit(&fa::fwd_kernel<false, 8, D, true>, mx);
       set_lds_limit(&fa::fwd_kernel<true, 8, D, true>, mx);
+      set_lds_limit(&fa::fwd_band_kernel<8, D>, mx);
     }
+    set_lds_limit(&fa::fwd_band_kernel<4, D>, mx);
     attr = true;
   }
   // 8 waves share each staged K/V tile when the query axis allows; head dim 256 runs 4 (register budget)
@@ -906,6 +1041,26 @@ static std::vector<at::Tensor> fwd_impl_d(at::Tensor q, at::Tensor k, at::Tensor
                        reinterpret_cast<unsigned short*>(o.data_ptr()), strides_of(o), lse.data_ptr<float>(), B, H, Hk,
                        Sq, Sk, (float)scale, causal ? 1 : 0, sp, kvlen, qoff);
   };
+  if (bd.klo != nullptr) {  // band mode: always the LDS-DMA forward (see fwd_band_kernel)
+    auto launch_band = [&](auto kern, int nwf) {
+      hipLaunchKernelGGL(kern, dim3(nwf == 8 ? grid / 2 : grid), dim3(nwf * 64), lds, cur_stream(),
+                         reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
+                         reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
+                         reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
+                         reinterpret_cast<unsigned short*>(o.data_ptr()), strides_of(o), lse.data_ptr<float>(), B, H,
+                         Hk, Sq, (float)scale, bd);
+    };
+    if constexpr (D < 256) {
+      if (wide) {
+        launch_band(fa::fwd_band_kernel<8, D>, 8);
+        SXE_LAUNCH_CHECK();
+        return {o, lse};
+      }
+    }
+    launch_band(fa::fwd_band_kernel<4, D>, 4);
+    SXE_LAUNCH_CHECK();
+    return {o, lse};
+  }
   if constexpr (D < 256) {
     if (fwd_dma()) {
       if (wide)
@@ -927,25 +1082,28 @@ static std::vector<at::Tensor> fwd_impl_d(at::Tensor q, at::Tensor k, at::Tensor
 }
 
 static std::vector<at::Tensor> fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
-                                        fa::Sparse sp, int64_t kv_len = -1, int64_t causal_offset = INT64_MIN) {
+                                        fa::Sparse sp, int64_t kv_len = -1, int64_t causal_offset = INT64_MIN,
+                                        fa::Band bd = fa::Band{nullptr, nullptr}) {
   check_qkv(q, k, v);
   const int Sq = q.size(1), Sk = k.size(1);
   const int kvlen = kv_len < 0 ? Sk : (int)kv_len;
   SXE_CHECK(kvlen >= 1 && kvlen <= Sk, "flash_attn: kv_len must be in [1, Sk]");
   const int qoff = causal_offset == INT64_MIN ? Sk - Sq : (int)causal_offset;
   SXE_CHECK(!sp.layout || (Sq == Sk && qoff == 0), "block-sparse attention needs Sq == Sk");
+  SXE_CHECK(!bd.klo || (causal && Sq == Sk && qoff == 0 && kvlen == Sk && !sp.layout),
+            "flash_attn band: needs causal, Sq == Sk, causal offset 0, no kv_len and no sparse layout");
   c10::DeviceGuard guard(q.device());
   switch (q.size(3)) {
-    case 64: return fwd_impl_d<64>(q, k, v, causal, scale, sp, kvlen, qoff);
-    case 256: return fwd_impl_d<256>(q, k, v, causal, scale, sp, kvlen, qoff);
-    default: return fwd_impl_d<128>(q, k, v, causal, scale, sp, kvlen, qoff);
+    case 64: return fwd_impl_d<64>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
+    case 256: return fwd_impl_d<256>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
+    default: return fwd_impl_d<128>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
   }
 }
 
 template <int D>
 static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
                        at::Tensor dq, at::Tensor dk, at::Tensor dv, bool causal, double scale, fa::Sparse sp,
-                       int kvlen, int qoff) {
+                       int kvlen, int qoff, fa::Band bd) {
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1), Hk = k.size(2);
   constexpr int ROWB = 2 * D;
   using G_ = fa::KVL<D>;
@@ -981,6 +1139,22 @@ static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v
       set_lds_limit(&fa::dkdv_kernel<false, D, 2>, lds_kv_max);
       set_lds_limit(&fa::dkdv_kernel<true, D, 2>, lds_kv_max);
     }
+    // band mode: the same variants, dense only
+    set_lds_limit(&fa::dq_band_kernel<D>, 4 * fa::KT * ROWB + kListBytes);
+    if constexpr (D < 256) set_lds_limit(&fa::dq_band_kernel<D, 8>, 4 * fa::KT * ROWB + kListBytes);
+    set_lds_limit(&fa::dkdv_band_kernel<false, D>, lds_kv_max);
+    set_lds_limit(&fa::dkdv_band_kernel<true, D>, lds_kv_max);
+    if constexpr (D == 128) {
+      const size_t mx8 = fa::KVL<D, 256>::VBLK + 2 * G_::SLOT + kListBytes;
+      set_lds_limit(&fa::dkdv_band_kernel<false, D, 3, 8>, mx8);
+      set_lds_limit(&fa::dkdv_band_kernel<true, D, 3, 8>, mx8);
+    }
+    if constexpr (D >= 256) {
+      set_lds_limit(&fa::dkdv_band_kernel<false, D, 1>, lds_kv_max);
+      set_lds_limit(&fa::dkdv_band_kernel<true, D, 1>, lds_kv_max);
+      set_lds_limit(&fa::dkdv_band_kernel<false, D, 2>, lds_kv_max);
+      set_lds_limit(&fa::dkdv_band_kernel<true, D, 2>, lds_kv_max);
+    }
     attr_set = true;
   }
   // 8-wave dQ workgroups from 8k queries on (auto; SXE_FA_DQ_WAVES=4 / 8 forces): 1.5-2 % faster
@@ -991,15 +1165,30 @@ static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v
   if constexpr (D < 256) {
     if (dq8) dqk = sp.layout ? fa::dq_kernel<true, D, 8> : fa::dq_kernel<false, D, 8>;
   }
-  hipLaunchKernelGGL(dqk, dim3((Sq / (dq8 ? 2 * fa::QB : fa::QB)) * B * H),
-                     dim3(dq8 ? 512 : 256), lds_dq, cur_stream(),
-                     reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                     reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                     reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                     reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                     lse.data_ptr<float>(), ndelta.data_ptr<float>(),
-                     reinterpret_cast<unsigned short*>(dq.data_ptr()), strides_of(dq), B, H, Hk, Sq, Sk, (float)scale,
-                     causal ? 1 : 0, sp, kvlen, qoff);
+  if (bd.klo != nullptr) {
+    auto* dqb = fa::dq_band_kernel<D>;
+    if constexpr (D < 256) {
+      if (dq8) dqb = fa::dq_band_kernel<D, 8>;
+    }
+    hipLaunchKernelGGL(dqb, dim3((Sq / (dq8 ? 2 * fa::QB : fa::QB)) * B * H), dim3(dq8 ? 512 : 256), lds_dq,
+                       cur_stream(), reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
+                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
+                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
+                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
+                       lse.data_ptr<float>(), ndelta.data_ptr<float>(),
+                       reinterpret_cast<unsigned short*>(dq.data_ptr()), strides_of(dq), B, H, Hk, Sq, (float)scale,
+                       bd);
+  } else {
+    hipLaunchKernelGGL(dqk, dim3((Sq / (dq8 ? 2 * fa::QB : fa::QB)) * B * H),
+                       dim3(dq8 ? 512 : 256), lds_dq, cur_stream(),
+                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
+                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
+                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
+                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
+                       lse.data_ptr<float>(), ndelta.data_ptr<float>(),
+                       reinterpret_cast<unsigned short*>(dq.data_ptr()), strides_of(dq), B, H, Hk, Sq, Sk,
+                       (float)scale, causal ? 1 : 0, sp, kvlen, qoff);
+  }
   SXE_LAUNCH_CHECK();
   // sparse: always one workgroup per query head (per-head tile lists); with GQA the per-head fp32
   // partials are reduced; causal GQA: split to remove the key-block-0 tail (see dkdv_kernel)
@@ -1050,9 +1239,39 @@ static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v
                        partials ? pk.data_ptr<float>() : nullptr, partials ? pv.data_ptr<float>() : nullptr, B, H, Hk,
                        Sq, Sk, (float)scale, causal ? 1 : 0, sp, qoff, hpw);
   };
+  auto launch_band = [&](auto kern, int heads, int nwk = 4) {
+    hipLaunchKernelGGL(kern, dim3((Sk / (nwk * fa::QW)) * B * heads), dim3(nwk * 64), lds_kv, cur_stream(),
+                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
+                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
+                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
+                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
+                       lse2.data_ptr<float>(), ndelta.data_ptr<float>(),
+                       reinterpret_cast<unsigned short*>(dk.data_ptr()), strides_of(dk),
+                       reinterpret_cast<unsigned short*>(dv.data_ptr()), strides_of(dv),
+                       partials ? pk.data_ptr<float>() : nullptr, partials ? pv.data_ptr<float>() : nullptr, B, H, Hk,
+                       Sq, (float)scale, hpw, bd);
+  };
   // the dK/dV launch(es) of one form: SPLIT = one workgroup per query-head group (partials / direct)
   auto run_dkdv = [&](auto splitc, int heads) {
     constexpr bool SP = decltype(splitc)::value;
+    if (bd.klo != nullptr) {  // band mode: the same variant choice
+      if constexpr (D >= 256) {
+        if (!one_sweep) {
+          launch_band(fa::dkdv_band_kernel<SP, D, 1>, heads);
+          SXE_LAUNCH_CHECK();
+          launch_band(fa::dkdv_band_kernel<SP, D, 2>, heads);
+          return;
+        }
+      }
+      if constexpr (D == 128) {
+        if (kv8) {
+          launch_band(fa::dkdv_band_kernel<SP, D, 3, 8>, heads, 8);
+          return;
+        }
+      }
+      launch_band(fa::dkdv_band_kernel<SP, D>, heads);
+      return;
+    }
     if constexpr (D >= 256) {
       if (!one_sweep) {
         launch(fa::dkdv_kernel<SP, D, 1>, heads);
@@ -1088,7 +1307,8 @@ static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v
 // dq/dk/dv are caller-provided (possibly strided views of one dqkv buffer).
 static void bwd_impl(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
                      at::Tensor dq, at::Tensor dk, at::Tensor dv, bool causal, double scale, fa::Sparse sp,
-                     int64_t kv_len = -1, int64_t causal_offset = INT64_MIN) {
+                     int64_t kv_len = -1, int64_t causal_offset = INT64_MIN,
+                     fa::Band bd = fa::Band{nullptr, nullptr}) {
   check_qkv(q, k, v);
   check_qkv(dq, dk, dv);
   const int Sq = q.size(1), Sk = k.size(1);
@@ -1099,11 +1319,13 @@ static void bwd_impl(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, 
             "flash_attn_bwd: dout/o shapes");
   SXE_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes(), "flash_attn_bwd: grad shapes");
   SXE_CHECK(lse.is_contiguous() && lse.size(2) == Sq, "flash_attn_bwd: lse [B, H, Sq]");
+  SXE_CHECK(!bd.klo || (causal && Sq == Sk && qoff == 0 && kvlen == Sk && !sp.layout),
+            "flash_attn_bwd band: needs causal, Sq == Sk, causal offset 0, no kv_len and no sparse layout");
   c10::DeviceGuard guard(q.device());
   switch (q.size(3)) {
-    case 64: return bwd_impl_d<64>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff);
-    case 256: return bwd_impl_d<256>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff);
-    default: return bwd_impl_d<128>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff);
+    case 64: return bwd_impl_d<64>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
+    case 256: return bwd_impl_d<256>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
+    default: return bwd_impl_d<128>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
   }
 }
 
@@ -1132,6 +1354,19 @@ void flash_attn_bwd_sparse(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tens
   bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sparse_of(layout, block, q));
 }
 
+// Band mask on top of the causal one (packed documents, sliding window; see fa::Band): query i sees
+// keys klo[b, i] <= j <= i, and qhi[b, j] is the last query that sees key j.
+std::vector<at::Tensor> flash_attn_fwd_band(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor klo, at::Tensor qhi,
+                                            double scale) {
+  return fwd_impl(q, k, v, true, scale, fa::Sparse{nullptr, 0, 0}, -1, INT64_MIN, band_of(klo, qhi, q, k));
+}
+
+void flash_attn_bwd_band(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
+                         at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor klo, at::Tensor qhi, double scale) {
+  bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, true, scale, fa::Sparse{nullptr, 0, 0}, -1, INT64_MIN,
+           band_of(klo, qhi, q, k));
+}
+
 }  // namespace sxe
 
 TORCH_LIBRARY_FRAGMENT(sxe, m) {
@@ -1143,10 +1378,15 @@ TORCH_LIBRARY_FRAGMENT(sxe, m) {
   m.def("flash_attn_fwd_sparse(Tensor q, Tensor k, Tensor v, Tensor layout, int block, bool causal, float scale) -> Tensor[]");
   m.def("flash_attn_bwd_sparse(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, "
         "Tensor(b!) dk, Tensor(c!) dv, Tensor layout, int block, bool causal, float scale) -> ()");
+  m.def("flash_attn_fwd_band(Tensor q, Tensor k, Tensor v, Tensor klo, Tensor qhi, float scale) -> Tensor[]");
+  m.def("flash_attn_bwd_band(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, "
+        "Tensor(b!) dk, Tensor(c!) dv, Tensor klo, Tensor qhi, float scale) -> ()");
 }
 TORCH_LIBRARY_IMPL(sxe, CUDA, m) {
   m.impl("flash_attn_fwd", &sxe::flash_attn_fwd);
   m.impl("flash_attn_bwd", &sxe::flash_attn_bwd);
   m.impl("flash_attn_fwd_sparse", &sxe::flash_attn_fwd_sparse);
   m.impl("flash_attn_bwd_sparse", &sxe::flash_attn_bwd_sparse);
+  m.impl("flash_attn_fwd_band", &sxe::flash_attn_fwd_band);
+  m.impl("flash_attn_bwd_band", &sxe::flash_attn_bwd_band);
 }

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from ..ops.mlp import swiglu_mlp
 from ..runtime.activation_checkpointing.checkpointing import checkpoint
 from ..runtime.zero.partition_parameters import local_shard
-from ..ops.attention import attention_qkv_rope, qkv_proj_attention
+from ..ops.attention import attention_qkv_rope, band_bounds, qkv_proj_attention
 from ..ops.cross_entropy import fused_linear_cross_entropy
 from ..ops.linear import Embedding, Linear, linear
 from ..ops.norm import RMSNorm
@@ -70,11 +70,16 @@ class LlamaConfig:
     fpdt_chunk_size: int = 0         # >0: FPDT chunked attention (global chunk length); inputs laid
                                      # out by sequence.fpdt_layer.FPDT_InputConstruct
     fpdt_offload: bool = False       # FPDT: keep the saved q/k/v/o chunks in pinned host memory
+    sliding_window: Optional[int] = None  # Mistral / Qwen2: a query sees the last N keys, itself included
+    packed_samples: bool = False     # rows are concatenated documents: one starts wherever position_ids
+                                     # is 0, and attention does not cross the boundaries
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
         if self.ac_policy not in ("full", "mlp"):
             raise ValueError(f"ac_policy must be 'full' or 'mlp', got {self.ac_policy!r}")
+        if self.sliding_window is not None and self.sliding_window < 1:
+            raise ValueError(f"sliding_window must be >= 1, got {self.sliding_window}")
         if self.head_dim is None:
             self.head_dim = self.hidden_size // self.num_attention_heads
 
@@ -127,15 +132,21 @@ class LlamaAttention(nn.Module):
         self.qkv_proj._tp_layout = ("heads", [self.nq, self.nkv, self.nkv], self.d)
         self.o_proj._tp_row_parallel = True
 
-    def forward(self, x, rope: RopeCache, position_ids=None):
+    def forward(self, x, rope: RopeCache, position_ids=None, bounds=None):
+        """``bounds``: band mask (packed documents / sliding window) of the whole sequence, built
+        once per step by ``LlamaForCausalLM.forward``."""
         B, S, _ = x.shape
         spg = _sp_group() if self.cfg.sequence_parallel else None
         if not self.cfg.fpdt_chunk_size and spg is None:
             # QKV projection + attention as one node: its weight gradient runs on token-minor
             # operands (ops/attention.py _QKVProjAttn)
-            o = qkv_proj_attention(x, self.qkv_proj, self.nq, self.nkv, rope, position_ids, causal=True)
+            o = qkv_proj_attention(x, self.qkv_proj, self.nq, self.nkv, rope, position_ids, causal=True,
+                                   bounds=bounds)
             return self.o_proj(o.reshape(B, S, self.nq * self.d))
         qkv = self.qkv_proj(x).view(B, S, self.nq + 2 * self.nkv, self.d)
+        if bounds is not None and (self.cfg.fpdt_chunk_size or self.cfg.sp_mode in ("ring", "ring_zigzag")):
+            raise NotImplementedError("packed_samples / sliding_window: ring attention and FPDT do not take a "
+                                      "document or window mask; use sp_mode='ulysses' or no sequence parallelism")
         if self.cfg.fpdt_chunk_size:
             from ..sequence.fpdt_layer import fpdt_attention
             from .. import comm as dist
@@ -146,9 +157,9 @@ class LlamaAttention(nn.Module):
             o = ring_qkv_attention(qkv, self.nq, self.nkv, rope, spg, position_ids, causal=True,
                                    layout="zigzag" if self.cfg.sp_mode == "ring_zigzag" else "contiguous")
         elif spg is not None:
-            o = ulysses_qkv_attention(qkv, self.nq, self.nkv, rope, spg, position_ids, causal=True)
+            o = ulysses_qkv_attention(qkv, self.nq, self.nkv, rope, spg, position_ids, causal=True, bounds=bounds)
         else:
-            o = attention_qkv_rope(qkv, self.nq, self.nkv, rope, position_ids, causal=True)
+            o = attention_qkv_rope(qkv, self.nq, self.nkv, rope, position_ids, causal=True, bounds=bounds)
         return self.o_proj(o.reshape(B, S, self.nq * self.d))
 
     def tp_shard_(self, tp):
@@ -181,13 +192,13 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp = LlamaMLP(cfg)
         self.ckpt_mlp = cfg.activation_checkpointing and cfg.ac_policy == "mlp"
 
-    def forward(self, x, residual, rope, position_ids=None):
+    def forward(self, x, residual, rope, position_ids=None, bounds=None):
         """(x, residual) -> (mlp_out, new_residual); the true hidden state is x + residual."""
         if residual is None:
             a, h = self.input_layernorm(x), x
         else:
             a, h = self.input_layernorm(x, residual)
-        attn = self.self_attn(a, rope, position_ids)
+        attn = self.self_attn(a, rope, position_ids, bounds)
         m, h2 = self.post_attention_layernorm(attn, h)
         if self.ckpt_mlp and self.training and torch.is_grad_enabled():
             return checkpoint(self.mlp, m), h2
@@ -273,15 +284,43 @@ class LlamaForCausalLM(nn.Module):
             self._rope = RopeCache(self.cfg.head_dim, self.cfg.max_position_embeddings, self.cfg.rope_theta, device)
         return self._rope
 
+    def attention_bounds(self, input_ids, position_ids):
+        """Band mask of this step (ops.attention.band_bounds), or None for plain causal attention:
+        document starts from ``position_ids`` when ``packed_samples``, plus ``sliding_window``.
+        Under sequence parallelism the inputs are this rank's shard; the bounds describe the whole
+        sequence (gathered ``position_ids``), which is what Ulysses attends over."""
+        cfg = self.cfg
+        packed = cfg.packed_samples and position_ids is not None
+        if not packed and cfg.sliding_window is None:
+            return None
+        if cfg.fpdt_chunk_size or (cfg.sequence_parallel and cfg.sp_mode in ("ring", "ring_zigzag")):
+            raise NotImplementedError("packed_samples / sliding_window: ring attention and FPDT do not take a "
+                                      "document or window mask; use sp_mode='ulysses' or no sequence parallelism")
+        B, S = input_ids.shape
+        pos = position_ids.reshape(-1, S).expand(B, S) if packed else None
+        spg = _sp_group() if cfg.sequence_parallel else None
+        if spg is not None:
+            from .. import comm as dist
+            p = dist.get_world_size(spg)
+            if pos is not None:
+                parts = [torch.empty_like(pos) for _ in range(p)]
+                dist.all_gather(parts, pos.contiguous(), group=spg)
+                pos = torch.cat(parts, dim=1)
+            S = S * p
+        return band_bounds(S, B, input_ids.device, position_ids=pos, window=cfg.sliding_window)
+
     def forward(self, input_ids, labels=None, position_ids=None, shift_labels=True):
         x = self.embed_tokens(input_ids)
         rope = self.rope(x.device)
+        bounds = self.attention_bounds(input_ids, position_ids)
         res = None
+        # layers (and whatever wraps or replaces them) keep today's call when there is no band mask
+        extra = () if bounds is None else (bounds,)
         for i, layer in enumerate(self.layers):
             if (self.cfg.activation_checkpointing and self.cfg.ac_policy == "full" and self.training
                     and torch.is_grad_enabled() and _ac_covers(self.cfg, i)):
-                x, res = checkpoint(layer, x, res, rope, position_ids)
+                x, res = checkpoint(layer, x, res, rope, position_ids, *extra)
             else:
-                x, res = layer(x, res, rope, position_ids)
+                x, res = layer(x, res, rope, position_ids, *extra)
         h = self.norm(x, res)[0] if res is not None else self.norm(x)
         return self.lm_head(h, labels, shift_labels=shift_labels)

@@ -16,6 +16,12 @@ dims (80, 96, 160, ...) are zero-padded to the next native one (zero q/k columns
 unchanged, zero v columns produce zero output columns that are dropped). The softmax scale is the
 true head dim's. ``SXE_ATTN_BACKEND=sdpa`` forces the stopgap for A/B comparisons.
 
+Band masks (``bounds=band_bounds(...)``): packed documents and / or a sliding window restrict the
+causal mask to keys ``klo[b, i] <= j <= i``. On the GPU the band variants of the same kernels run
+(``flash_attn_fwd_band`` / ``flash_attn_bwd_band``): they skip the K/V tiles below the band, so a row
+of eight equal documents costs about an eighth of the causal work. Padded shapes append the pad
+tokens as one trailing document; CPU and uncovered cases build the boolean mask and call SDPA.
+
 ``attention_qkv_rope`` is the training entry point of the Llama family: it takes the fused QKV
 projection output [B, S, Hq + 2*Hkv, D], applies RoPE in place, runs attention reading q/k/v as
 strided views, and in backward writes dq/dk/dv straight into ONE dqkv buffer (then rotates the
@@ -31,7 +37,66 @@ from . import native
 from ..utils.logging import warning_once
 
 
-def _sdpa(q, k, v, causal, scale):
+def band_bounds(S, B, device, position_ids=None, doc_ids=None, window=None):
+    """(klo, qhi), int32 [B, S] on ``device``: query i sees keys klo[b, i] <= j <= i, and qhi[b, j] is
+    the last query that sees key j. A document starts where ``position_ids == 0`` (the HF packed-sample
+    convention) or where ``doc_ids`` changes; ``window=W`` keeps the last W keys including the query
+    itself (as ``window`` in ops/paged_attention.py). Documents and window combine by max (klo) / min
+    (qhi). Returns None when neither is given. Torch ops on the device only: no host synchronisation."""
+    if position_ids is None and doc_ids is None and window is None:
+        return None
+    idx = torch.arange(S, device=device, dtype=torch.int32).expand(B, S)
+    klo = torch.zeros(B, S, dtype=torch.int32, device=device)
+    qhi = torch.full((B, S), S - 1, dtype=torch.int32, device=device)
+    start = None
+    if position_ids is not None:
+        start = (position_ids.to(device).reshape(-1, S) == 0).expand(B, S)
+    if doc_ids is not None:
+        d = doc_ids.to(device).reshape(-1, S).expand(B, S)
+        chg = torch.ones(B, S, dtype=torch.bool, device=device)
+        chg[:, 1:] = d[:, 1:] != d[:, :-1]
+        start = chg if start is None else (start | chg)
+    if start is not None:
+        zero = torch.zeros_like(idx)
+        klo = torch.cummax(torch.where(start, idx, zero), dim=1).values.to(torch.int32)
+        # the next document start after key j (S when there is none), minus one
+        nxt = torch.full((B, S + 1), S, dtype=torch.int32, device=device)
+        nxt[:, :S] = torch.where(start, idx, torch.full_like(idx, S))
+        nxt = torch.cummin(nxt.flip(1), dim=1).values.flip(1)
+        qhi = (nxt[:, 1:] - 1).to(torch.int32)
+    if window is not None:
+        W = int(window)
+        if W < 1:
+            raise ValueError(f"window must be >= 1, got {window}")
+        klo = torch.maximum(klo, (idx - (W - 1)).clamp_min(0))
+        qhi = torch.minimum(qhi, (idx + (W - 1)).clamp_max(S - 1))
+    return klo.contiguous(), qhi.contiguous()
+
+
+def band_mask(bounds, S):
+    """Boolean [B, S, S] mask of the band (True = visible), with the kernels' clamp of klo to [0, i]."""
+    klo = bounds[0]
+    i = torch.arange(S, device=klo.device)
+    lo = torch.minimum(klo.long().clamp_min(0), i)
+    return (i[None, None, :] >= lo[:, :, None]) & (i[None, None, :] <= i[None, :, None])
+
+
+def _check_band(q, k, causal, bounds):
+    if not causal or q.shape[1] != k.shape[1]:
+        raise ValueError("attention bounds need causal=True and equal query / key lengths")
+    klo, qhi = bounds
+    if tuple(klo.shape) != (q.shape[0], q.shape[1]) or tuple(qhi.shape) != tuple(klo.shape):
+        raise ValueError(f"attention bounds must be [B, S] = {(q.shape[0], q.shape[1])}, got {tuple(klo.shape)}")
+
+
+def _sdpa(q, k, v, causal, scale, mask=None):
+    if mask is not None:  # band mask [B, S, S] (already causal)
+        qt, kt, vt = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
+        if qt.shape[1] != kt.shape[1]:
+            rep = qt.shape[1] // kt.shape[1]
+            kt, vt = kt.repeat_interleave(rep, dim=1), vt.repeat_interleave(rep, dim=1)
+        o = F.scaled_dot_product_attention(qt, kt, vt, attn_mask=mask[:, None], scale=scale)
+        return o.transpose(1, 2)
     qt, kt, vt = q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2)
     gqa = qt.shape[1] != kt.shape[1]
     if gqa and not q.is_cuda:
@@ -140,10 +205,81 @@ class _FlashAttn(torch.autograd.Function):
         return dq, dk, dv, None, None
 
 
-def attention(q, k, v, causal=True, softmax_scale=None):
+def _pad_bounds(bounds, S_pad):
+    """Bounds for a sequence zero-padded to S_pad: the pad tokens form one trailing document."""
+    klo, qhi = bounds
+    B, S = klo.shape
+    if S == S_pad:
+        return klo, qhi
+    kp = torch.full((B, S_pad), S, dtype=torch.int32, device=klo.device)
+    qp = torch.full((B, S_pad), S_pad - 1, dtype=torch.int32, device=klo.device)
+    kp[:, :S] = klo
+    qp[:, :S] = qhi.clamp_max(S - 1)
+    return kp, qp
+
+
+class _FlashAttnBand(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, klo, qhi, scale):
+        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
+        ctx.save_for_backward(q, k, v, o, lse, klo, qhi)
+        ctx.scale = scale
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        q, k, v, o, lse, klo, qhi = ctx.saved_tensors
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(ctx.scale))
+        return dq, dk, dv, None, None, None
+
+
+class _FlashAttnBandPadded(torch.autograd.Function):
+    """Band attention on padded copies: the pad tokens are one trailing document, so no real query
+    sees a pad key and the kernels' ``kv_len`` is not needed."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, klo, qhi, scale):
+        S, D = q.shape[1], q.shape[-1]
+        Dp, Sp = _native_dim(D), -(-S // TILE) * TILE
+        qp, kp, vp = _pad(q, Sp, Dp), _pad(k, Sp, Dp), _pad(v, Sp, Dp)
+        klo, qhi = _pad_bounds((klo, qhi), Sp)
+        o, lse = torch.ops.sxe.flash_attn_fwd_band(qp, kp, vp, klo, qhi, float(scale))
+        ctx.save_for_backward(qp, kp, vp, o, lse, klo, qhi)
+        ctx.meta = (scale, S, D, q.dtype)
+        return o[:, :S, :, :D].to(q.dtype)
+
+    @staticmethod
+    def backward(ctx, do):
+        qp, kp, vp, o, lse, klo, qhi = ctx.saved_tensors
+        scale, S, D, dtype = ctx.meta
+        dop = _pad(do, qp.shape[1], qp.shape[-1])
+        dq, dk, dv = torch.empty_like(qp), torch.empty_like(kp), torch.empty_like(vp)
+        torch.ops.sxe.flash_attn_bwd_band(dop, qp, kp, vp, o, lse, dq, dk, dv, klo, qhi, float(scale))
+        sl = (slice(None), slice(0, S), slice(None), slice(0, D))
+        return dq[sl].to(dtype), dk[sl].to(dtype), dv[sl].to(dtype), None, None, None
+
+
+def _attention_band(q, k, v, causal, scale, bounds):
+    _check_band(q, k, causal, bounds)
+    if q.is_cuda:
+        native.require_hip()
+        if hip_supported(q, k, v):
+            return _FlashAttnBand.apply(q, k, v, bounds[0], bounds[1], scale)
+        if hip_paddable(q, k, v):
+            return _FlashAttnBandPadded.apply(q, k, v, bounds[0], bounds[1], scale)
+        warning_once(f"sxe attention: HIP flash kernel does not cover dtype={q.dtype} D={q.shape[-1]} "
+                     f"S={q.shape[1]}; using SDPA")
+    return _sdpa(q, k, v, True, scale, band_mask(bounds, q.shape[1]))
+
+
+def attention(q, k, v, causal=True, softmax_scale=None, bounds=None):
     """q: [B, Sq, Hq, D], k/v: [B, Sk, Hkv, D] (strided views allowed) -> [B, Sq, Hq, D]. With Sq != Sk
-    and ``causal`` the mask is bottom-right aligned (query i sees keys <= i + Sk - Sq)."""
+    and ``causal`` the mask is bottom-right aligned (query i sees keys <= i + Sk - Sq). ``bounds``
+    (from ``band_bounds``; needs causal and Sq == Sk) narrows the mask to packed documents / a window."""
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if bounds is not None:
+        return _attention_band(q, k, v, causal, scale, bounds)
     if q.is_cuda:
         native.require_hip()
         if hip_supported(q, k, v):
@@ -183,8 +319,36 @@ class _FlashAttnQKVRope(torch.autograd.Function):
         return dqkv, None, None, None, None, None, None, None
 
 
-def attention_qkv_rope(qkv, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None):
-    """qkv: [B, S, nq + 2*nkv, D] fused projection output. Returns o [B, S, nq, D]."""
+class _FlashAttnQKVRopeBand(torch.autograd.Function):
+    """``_FlashAttnQKVRope`` with a band mask (causal)."""
+
+    @staticmethod
+    def forward(ctx, qkv, cos, sin, nq, nkv, scale, pos, klo, qhi):
+        S = qkv.shape[1]
+        if cos is not None:
+            torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
+        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
+        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
+        ctx.save_for_backward(qkv, o, lse, cos, sin, pos, klo, qhi)  # see _FlashAttnQKVRope on qkv
+        ctx.meta = (nq, nkv, scale)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        qkv, o, lse, cos, sin, pos, klo, qhi = ctx.saved_tensors
+        nq, nkv, scale = ctx.meta
+        dqkv = torch.empty_like(qkv)
+        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
+        dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
+        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(scale))
+        if cos is not None:
+            torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, qkv.shape[1], 0, True)
+        return dqkv, None, None, None, None, None, None, None, None
+
+
+def attention_qkv_rope(qkv, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None, bounds=None):
+    """qkv: [B, S, nq + 2*nkv, D] fused projection output. Returns o [B, S, nq, D]. ``bounds``: see
+    ``attention``."""
     D = qkv.shape[-1]
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)
     q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
@@ -194,12 +358,15 @@ def attention_qkv_rope(qkv, nq, nkv, rope=None, position_ids=None, causal=True, 
             pos = position_ids.reshape(-1).contiguous().long() if position_ids is not None else None
             cos = rope.cos if rope is not None else None
             sin = rope.sin if rope is not None else None
+            if bounds is not None:
+                _check_band(q, k, causal, bounds)
+                return _FlashAttnQKVRopeBand.apply(qkv, cos, sin, nq, nkv, scale, pos, bounds[0], bounds[1])
             return _FlashAttnQKVRope.apply(qkv, cos, sin, nq, nkv, causal, scale, pos)
     if rope is not None:
         from .rope import apply_rope_qkv_
         qkv = apply_rope_qkv_(qkv, rope, nq + nkv, position_ids)
     q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-    return attention(q, k, v, causal, scale)
+    return attention(q, k, v, causal, scale, bounds)
 
 
 QKV_TN = os.environ.get("SXE_QKV_TN", "1") == "1"
@@ -246,9 +413,49 @@ class _QKVProjAttn(torch.autograd.Function):
         return dx, dw, None, None, None, None, None, None, None
 
 
-def qkv_proj_attention(x, qkv_proj, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None):
+class _QKVProjAttnBand(torch.autograd.Function):
+    """``_QKVProjAttn`` with a band mask (causal)."""
+
+    @staticmethod
+    def forward(ctx, x, w, cos, sin, nq, nkv, scale, pos, klo, qhi):
+        B, S, H = x.shape
+        x2 = x.reshape(-1, H)
+        qkv = F.linear(x2, w).view(B, S, nq + 2 * nkv, -1)
+        if cos is not None:
+            torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
+        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
+        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
+        xT = torch.ops.sxe.transpose16(x2) if ctx.needs_input_grad[1] else None
+        ctx.save_for_backward(xT, qkv, o, lse, cos, sin, pos, w, klo, qhi)
+        ctx.meta = (nq, nkv, scale, x.shape)
+        return o
+
+    @staticmethod
+    def backward(ctx, do):
+        xT, qkv, o, lse, cos, sin, pos, w, klo, qhi = ctx.saved_tensors
+        nq, nkv, scale, x_shape = ctx.meta
+        dqkv = torch.empty_like(qkv)
+        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
+        dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
+        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(scale))
+        del q, k, v, o, lse, qkv
+        if cos is not None:
+            torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, dqkv.shape[1], 0, True)
+        d2 = dqkv.view(-1, w.shape[0])
+        from .linear import data_grad
+        from .mlp import weight_grad_tn
+        dx = data_grad(d2, w).view(x_shape) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            dw = weight_grad_tn(w, torch.ops.sxe.transpose16(d2), xT, fp32_out=True)
+        return dx, dw, None, None, None, None, None, None, None, None
+
+
+def qkv_proj_attention(x, qkv_proj, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None,
+                       bounds=None):
     """``attention_qkv_rope(qkv_proj(x))`` for x [B, S, H]; one fused autograd node (``_QKVProjAttn``)
-    when the shapes, dtypes and the plain bias-free projection allow, else the two-step path."""
+    when the shapes, dtypes and the plain bias-free projection allow, else the two-step path.
+    ``bounds``: see ``attention``."""
     B, S, H = x.shape
     w = getattr(qkv_proj, "weight", None)
     from .mlp import _plain
@@ -263,9 +470,13 @@ def qkv_proj_attention(x, qkv_proj, nq, nkv, rope=None, position_ids=None, causa
             pos = position_ids.reshape(-1).contiguous().long() if position_ids is not None else None
             cos = rope.cos if rope is not None else None
             sin = rope.sin if rope is not None else None
+            if bounds is not None:
+                if not causal or tuple(bounds[0].shape) != (B, S) or tuple(bounds[1].shape) != (B, S):
+                    raise ValueError("attention bounds need causal=True and [B, S] tensors")
+                return _QKVProjAttnBand.apply(x, w, cos, sin, nq, nkv, scale, pos, bounds[0], bounds[1])
             return _QKVProjAttn.apply(x, w, cos, sin, nq, nkv, causal, scale, pos)
     qkv = qkv_proj(x).view(B, S, N, -1)
-    return attention_qkv_rope(qkv, nq, nkv, rope, position_ids, causal, softmax_scale)
+    return attention_qkv_rope(qkv, nq, nkv, rope, position_ids, causal, softmax_scale, bounds)
 
 
 def attention_with_lse(q, k, v, causal=True, softmax_scale=None):
@@ -280,8 +491,9 @@ def attention_with_lse(q, k, v, causal=True, softmax_scale=None):
     return reference_attention(q, k, v, causal, scale, return_lse=True)
 
 
-def reference_attention(q, k, v, causal=True, scale=None, return_lse=False):
-    """fp32 eager oracle used by the tests (and the CPU path of attention_with_lse)."""
+def reference_attention(q, k, v, causal=True, scale=None, return_lse=False, bounds=None):
+    """fp32 eager oracle used by the tests (and the CPU path of attention_with_lse). ``bounds``: the
+    band mask of ``band_bounds`` on top of the causal one."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     qt, kt, vt = q.transpose(1, 2).float(), k.transpose(1, 2).float(), v.transpose(1, 2).float()
     if kt.shape[1] != qt.shape[1]:
@@ -292,6 +504,9 @@ def reference_attention(q, k, v, causal=True, scale=None, return_lse=False):
         S, T = s.shape[-2], s.shape[-1]
         mask = torch.ones(S, T, dtype=torch.bool, device=s.device).tril(T - S)
         s = s.masked_fill(~mask, float("-inf"))
+    if bounds is not None:
+        _check_band(q, k, causal, bounds)
+        s = s.masked_fill(~band_mask(bounds, s.shape[-1])[:, None], float("-inf"))
     lse = torch.logsumexp(s, dim=-1)
     o = torch.matmul(torch.softmax(s, dim=-1), vt).transpose(1, 2).to(q.dtype)
     return (o, lse) if return_lse else o

@@ -79,6 +79,17 @@ def _fa_bwd(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, kv_len=-1, causal_
     return None
 
 
+@_reg("sxe::flash_attn_fwd_band")
+def _fa_fwd_band(q, k, v, klo, qhi, scale):
+    B, Sq, H, D = q.shape
+    return [q.new_empty((B, Sq, H, v.shape[-1])), q.new_empty((B, H, Sq), dtype=torch.float32)]
+
+
+@_reg("sxe::flash_attn_bwd_band")
+def _fa_bwd_band(dout, q, k, v, o, lse, dq, dk, dv, klo, qhi, scale):
+    return None
+
+
 @_reg("sxe::xent_fwd")
 def _xent_fwd(logits, target, ignore_index, inplace_grad, scale, grad_scale):
     r = logits.shape[0]

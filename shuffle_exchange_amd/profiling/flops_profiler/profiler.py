@@ -53,6 +53,16 @@ def _register_sxe_formulas():
             causal = a[3] if len(a) > 3 else True
             return int(2.5 * attn_flops(q, k, causal))
 
+        # band mode (packed documents / sliding window): counted as plain causal attention, an
+        # upper bound -- the visible fraction depends on the bounds' values, not on the shapes
+        @register_flop_formula(ops.flash_attn_fwd_band)
+        def _fa_fwd_band(q, k, v, *a, out_shape=None, **kw):
+            return attn_flops(q, k, True)
+
+        @register_flop_formula(ops.flash_attn_bwd_band)
+        def _fa_bwd_band(dout, q, k, v, *a, out_shape=None, **kw):
+            return int(2.5 * attn_flops(q, k, True))
+
         # hand-written GEMMs: 2 * rows * out * in
         @register_flop_formula(ops.skinny_gemm)
         def _skinny(x, w, *a, out_shape=None, **kw):

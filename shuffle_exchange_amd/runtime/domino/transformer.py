@@ -62,14 +62,17 @@ class DominoLlamaDecoderLayer(LlamaDecoderLayer):
     domino_micro_batches = 2
     overlapped_calls = 0  # forward calls that took the overlapped schedule (observability / tests)
 
-    def forward(self, x, residual, rope, position_ids=None):
+    def forward(self, x, residual, rope, position_ids=None, bounds=None):
         attn, mlp = self.self_attn, self.mlp
         group = attn.o_proj.tp_group
         n = self.domino_micro_batches
         if x.shape[0] < n or group is None or dist.get_world_size(group) == 1:
-            return super().forward(x, residual, rope, position_ids)
+            return super().forward(x, residual, rope, position_ids, bounds)
         DominoLlamaDecoderLayer.overlapped_calls += 1
         xs, rs, ps = _split(x, n), _split(residual, n), _split(position_ids, n)
+        # band mask (packed documents / sliding window): [B, S] bounds split along the batch like x
+        bs = [None] * n if bounds is None else [(lo.contiguous(), hi.contiguous()) for lo, hi in
+                                                zip(_split(bounds[0], n), _split(bounds[1], n))]
         gh = [[] for _ in range(n)]  # backward input-grad all-reduce handles per micro-batch
         fbox = [[] for _ in range(n)]  # forward all-reduce handles per micro-batch
         # ---- attention: micro-batch i+1's QKV/flash/o_proj GEMMs run under i's all-reduce
@@ -82,7 +85,7 @@ class DominoLlamaDecoderLayer(LlamaDecoderLayer):
             a = wait_grad_handles(a, gh[i])
             B, S = a.shape[0], a.shape[1]
             qkv = attn.qkv_proj(a, grad_handles=gh[i]).view(B, S, attn.nq + 2 * attn.nkv, attn.d)
-            o = attention_qkv_rope(qkv, attn.nq, attn.nkv, rope, ps[i], causal=True)
+            o = attention_qkv_rope(qkv, attn.nq, attn.nkv, rope, ps[i], causal=True, bounds=bs[i])
             y = attn.o_proj.forward_partial(o.reshape(B, S, attn.nq * attn.d))
             pend.append((_AsyncAllReduce.apply(y, group, fbox[i]), h))
         # ---- MLP: consume micro-batch i's reduced attention output, overlap its MLP with the rest

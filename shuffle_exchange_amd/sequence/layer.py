@@ -272,8 +272,10 @@ def _replicate_kv(qkv, nq, nkv, p):
     return torch.cat([q, k, v], dim=2), nkv * rep
 
 
-def ulysses_qkv_attention(qkv, nq, nkv, rope, group, position_ids=None, causal=True, softmax_scale=None):
-    """Sequence-parallel attention on a packed QKV chunk [B, S/p, nq+2nkv, D] -> [B, S/p, nq, D]."""
+def ulysses_qkv_attention(qkv, nq, nkv, rope, group, position_ids=None, causal=True, softmax_scale=None,
+                          bounds=None):
+    """Sequence-parallel attention on a packed QKV chunk [B, S/p, nq+2nkv, D] -> [B, S/p, nq, D].
+    ``bounds``: band mask of the WHOLE sequence (after the all-to-all every rank holds all of it)."""
     from ..ops.attention import attention_qkv_rope
     from ..ops.rope import apply_rope_qkv_
     p = dist.get_world_size(group)
@@ -288,5 +290,6 @@ def ulysses_qkv_attention(qkv, nq, nkv, rope, group, position_ids=None, causal=T
         qkv, nkv = _replicate_kv(qkv, nq, nkv, p)
     assert nq % p == 0 and nkv % p == 0, f"heads ({nq}, {nkv}) must be divisible by sp={p}"
     full = _QKVSeqToHead.apply(group, qkv, nq, nkv)  # [B, S, (nq+2nkv)/p, D]
-    o = attention_qkv_rope(full, nq // p, nkv // p, None, None, causal=causal, softmax_scale=softmax_scale)
+    o = attention_qkv_rope(full, nq // p, nkv // p, None, None, causal=causal, softmax_scale=softmax_scale,
+                           bounds=bounds)
     return _SeqAllToAll.apply(group, o, False)  # [B, S/p, nq, D]

@@ -121,16 +121,26 @@ def vocab_sequence_parallel_cross_entropy(logits, target, sp_group=None, ignore_
 
 
 # ----------------------------------------------------------------------------------- HF adapter
+_PACKED_SAMPLES = False  # set by register_with_transformers(packed_samples=True)
+
+
 def sxe_flash_attention_forward(module, query, key, value, attention_mask=None, dropout=0.0, scaling=None,
                                 is_causal=None, **kwargs):
     """HF ``ALL_ATTENTION_FUNCTIONS`` entry running the gfx950 flash kernel (ops/attention.py):
     q/k/v [B, H, S, D] in, ([B, S, H, D], None) out -- the HF attention-function convention. A
     causal (or absent) mask runs the fused causal kernel; an explicit non-causal 4-D mask, dropout
-    or an uncovered shape falls back to SDPA with the mask."""
-    from ..ops.attention import attention, hip_paddable, hip_supported
+    or an uncovered shape falls back to SDPA with the mask. After
+    ``register_with_transformers(packed_samples=True)`` the ``position_ids`` HF hands over (the whole
+    sequence: ``UlyssesSPAttentionHF`` gathers them) mark the packed documents -- one starts wherever
+    they are 0 -- and causal self-attention runs the band kernels, so no token sees another document."""
+    from ..ops.attention import attention, band_bounds, hip_paddable, hip_supported
     causal = getattr(module, "is_causal", True) if is_causal is None else bool(is_causal)
     q, k, v = (t.transpose(1, 2) for t in (query, key, value))
     plain = attention_mask is None or attention_mask.dim() != 4
+    pos = kwargs.get("position_ids") if _PACKED_SAMPLES else None
+    if pos is not None and plain and causal and not dropout and q.shape[1] == k.shape[1]:
+        bounds = band_bounds(q.shape[1], q.shape[0], q.device, position_ids=pos)
+        return attention(q, k, v, causal=True, softmax_scale=scaling, bounds=bounds), None
     if (query.is_cuda and plain and not dropout and (hip_supported(q, k, v) or hip_paddable(q, k, v))):
         return attention(q, k, v, causal=causal, softmax_scale=scaling), None
     if key.shape[1] != query.shape[1]:
@@ -204,12 +214,15 @@ class UlyssesSPAttentionHF:
 
 
 def register_with_transformers(model_config, core_attn_implementation=None, sequence_parallel_size=1,
-                               sp_group=None, name="ulysses"):
+                               sp_group=None, name="ulysses", packed_samples=False):
     """Register ``UlyssesSPAttentionHF`` as an HF attention implementation named ``name`` and return
     the configured callable (set ``config._attn_implementation = name`` on the model). The default
     core attention is the gfx950 flash kernel (registered as ``"sxe_flash"``); pass e.g. ``"sdpa"``
-    for an HF one."""
+    for an HF one. ``packed_samples=True`` (opt-in) makes ``"sxe_flash"`` honour the document
+    boundaries in ``position_ids`` (see ``sxe_flash_attention_forward``)."""
     from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+    global _PACKED_SAMPLES
+    _PACKED_SAMPLES = bool(packed_samples)
     ALL_ATTENTION_FUNCTIONS.register("sxe_flash", sxe_flash_attention_forward)
     core = ALL_ATTENTION_FUNCTIONS[core_attn_implementation or "sxe_flash"]
     if sp_group is None:

@@ -1,7 +1,10 @@
 """Time the flash attention kernels alone (fwd, fwd+bwd) vs SDPA, per head dim; for D < 128 also
 the old zero-padded-to-128 path, for Sq != Sk the prefix shape.
   python tools/attn_bench.py [B]
-  python tools/attn_bench.py --shapes B,Sq,Sk,H,Hk,D,causal[;...] [--no-sdpa]"""
+  python tools/attn_bench.py --shapes B,Sq,Sk,H,Hk,D,causal[;...] [--no-sdpa] [--docs N] [--window W]
+--docs N (N equal documents per row) and / or --window W time the band kernels on the causal
+self-attention shapes: flops count the truly visible (query, key) pairs, and the dense causal time
+at the same shape is printed beside it."""
 import json
 import sys
 import time
@@ -9,7 +12,7 @@ import time
 import torch
 
 sys.path.insert(0, '.')
-from shuffle_exchange_amd.ops.attention import _sdpa, attention  # noqa: E402
+from shuffle_exchange_amd.ops.attention import _sdpa, attention, band_bounds  # noqa: E402
 
 
 def t(fn, n=10):
@@ -21,6 +24,32 @@ def t(fn, n=10):
         fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n
+
+
+def run_band(B, S, H, Hk, D, docs, window):
+    q = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    k = torch.randn(B, S, Hk, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    v = torch.randn(B, S, Hk, D, device="cuda", dtype=torch.bfloat16, requires_grad=True)
+    g = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16)
+    doc_ids = (torch.arange(S, device="cuda") * docs // S).expand(B, S) if docs else None
+    bounds = band_bounds(S, B, "cuda", doc_ids=doc_ids, window=window)
+    idx = torch.arange(S, device="cuda")
+    visible = int((idx - bounds[0][0] + 1).sum())  # (query, key) pairs of one row
+    flops = 4 * B * H * D * visible
+    dense = lambda: attention(q, k, v, causal=True)  # noqa: E731
+    band = lambda: attention(q, k, v, causal=True, bounds=bounds)  # noqa: E731
+    tf, tb = t(band), t(lambda: torch.autograd.grad(band(), (q, k, v), g))
+    df, db = t(dense), t(lambda: torch.autograd.grad(dense(), (q, k, v), g))
+    print(json.dumps({"path": "hip_band", "B": B, "S": S, "H": H, "Hk": Hk, "D": D, "docs": docs, "window": window,
+                      "visible_frac_of_causal": round(visible / (S * (S + 1) / 2), 4),
+                      "fwd_ms": round(tf * 1e3, 3), "fwd_TF": round(flops / tf / 1e12, 1),
+                      "fwdbwd_ms": round(tb * 1e3, 3), "fwdbwd_TF": round(3.5 * flops / tb / 1e12, 1),
+                      "dense_causal_fwd_ms": round(df * 1e3, 3), "dense_causal_fwdbwd_ms": round(db * 1e3, 3),
+                      "fwd_speedup": round(df / tf, 2), "fwdbwd_speedup": round(db / tb, 2)}), flush=True)
+
+
+def _opt(name):
+    return int(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else None
 
 
 def run(B, Sq, Sk, H, Hk, D, causal=True, sdpa=True):
@@ -53,6 +82,10 @@ def main():
         spec = sys.argv[sys.argv.index("--shapes") + 1]
         for sh in spec.split(";"):
             B, Sq, Sk, H, Hk, D, c = (int(x) for x in sh.split(","))
+            if _opt("--docs") or _opt("--window"):
+                assert c and Sq == Sk, "--docs / --window need a causal self-attention shape"
+                run_band(B, Sq, H, Hk, D, _opt("--docs"), _opt("--window"))
+                continue
             run(B, Sq, Sk, H, Hk, D, causal=bool(c), sdpa="--no-sdpa" not in sys.argv)
         return
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4

@@ -40,7 +40,7 @@ def main():
         if filt in d["name"]:
             print(f"{d['name'][:70]:70s} VGPR {d.get('VGPRs', '?'):>4} AGPR {d.get('AGPRs', '?'):>4} "
                   f"spill {d.get('VGPRs Spill', '?'):>4} scratch {d.get('ScratchSize [bytes/lane]', '?'):>4} "
-                  f"occ {d.get('Occupancy [waves/SIMD]', '?')}")
+                  f"LDS {d.get('LDS Size [bytes/block]', '?'):>5} occ {d.get('Occupancy [waves/SIMD]', '?')}")
 
 
 if __name__ == "__main__":
