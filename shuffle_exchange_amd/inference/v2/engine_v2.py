@@ -63,6 +63,16 @@ class RaggedInferenceEngineConfig:
     decode_graphs: bool = True  # replay pure-decode steps from captured HIP graphs (decode_graphs.py)
     weight_quant: Optional[str] = None  # "fp8" (W8A16) | "fp6" / "wf6af16" (FP6-LLM) | "fp4": weight-only decode GEMMs
     implementations: Optional[dict] = None  # pin registry implementations by interface (modules/registry.py)
+    kv_cache_dtype: Optional[str] = None  # None / "bf16": the model dtype; "fp8": e4m3 codes + one fp32 scale per row
+
+
+KV_CACHE_DTYPES = (None, "bf16", "fp8")
+
+
+def _kv_dtype(name, model_dtype):
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {name!r}")
+    return torch.float8_e4m3fn if name == "fp8" else model_dtype
 
 
 _TP_GROUPS = {}
@@ -96,14 +106,16 @@ class InferenceEngineV2:
         tp = int((self._config.tensor_parallel or {}).get("tp_size", 1))
         self._tp = tp
         self._tp_group = _tp_group(tp) if tp > 1 else None
+        _kv_dtype(self._config.kv_cache_dtype, None)  # reject an unknown name before any work
         self._model = ragged_model_for(model, weight_quant=self._config.weight_quant, tp_group=self._tp_group,
                                        tp_size=tp, pins=self._config.implementations)
         sm = self._config.state_manager
         dev = self._model.device
         bs = self._config.kv_block_size
+        self._kv_dtype = _kv_dtype(self._config.kv_cache_dtype, self._model.dtype)
         nblocks = self._config.num_kv_blocks or self._size_cache(dev, bs)
         self._kv = BlockedKVCache(self._model.num_layers, nblocks, bs, self._model.nkv, self._model.head_dim,
-                                  dtype=self._model.dtype, device=dev)
+                                  dtype=self._kv_dtype, device=dev)
         max_blocks_seq = math.ceil(sm.max_context / bs)
         self._state = DSStateManager(self._kv, sm.max_tracked_sequences, max_blocks_seq)
         self._decode_graphs = None
@@ -121,7 +133,7 @@ class InferenceEngineV2:
                 budget = mc.size
             else:
                 budget = max(0, free - mc.size)
-        return BlockedKVCache.blocks_for_budget(budget, m.num_layers, bs, m.nkv, m.head_dim, m.dtype)
+        return BlockedKVCache.blocks_for_budget(budget, m.num_layers, bs, m.nkv, m.head_dim, self._kv_dtype)
 
     # ------------------------------------------------------------------------------------ API
     @property

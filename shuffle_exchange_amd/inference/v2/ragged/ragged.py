@@ -51,19 +51,34 @@ class BlockedAllocator:
 
 
 class BlockedKVCache:
+    """``dtype=torch.float8_e4m3fn``: ``cache`` holds the e4m3 codes and ``scales``
+    ([layers, blocks, 2, nkv, bs] fp32) one scale per cached row; ``layer(i)`` is then an
+    ``FP8KVLayer`` (format: ops/paged_attention.py)."""
+
     def __init__(self, num_layers, num_blocks, block_size, n_kv_heads, head_dim, dtype=torch.bfloat16, device=None):
         self.num_layers, self.num_blocks, self.block_size = num_layers, num_blocks, block_size
         self.n_kv_heads, self.head_dim = n_kv_heads, head_dim
         self.cache = torch.zeros(num_layers, num_blocks, 2, n_kv_heads, block_size, head_dim, dtype=dtype,
                                  device=device)
+        self.scales = None
+        if dtype == torch.float8_e4m3fn:
+            self.scales = torch.zeros(num_layers, num_blocks, 2, n_kv_heads, block_size, dtype=torch.float32,
+                                      device=device)
         self.allocator = BlockedAllocator(num_blocks)
 
     @staticmethod
     def blocks_for_budget(budget_bytes, num_layers, block_size, n_kv_heads, head_dim, dtype=torch.bfloat16):
-        per_block = num_layers * 2 * n_kv_heads * block_size * head_dim * torch.tensor([], dtype=dtype).element_size()
+        if dtype == torch.float8_e4m3fn:
+            row_bytes = head_dim + 4  # one code byte per element + the row's fp32 scale
+        else:
+            row_bytes = head_dim * torch.tensor([], dtype=dtype).element_size()
+        per_block = num_layers * 2 * n_kv_heads * block_size * row_bytes
         return max(1, int(budget_bytes // per_block))
 
     def layer(self, i):
+        if self.scales is not None:
+            from ....ops.paged_attention import FP8KVLayer
+            return FP8KVLayer(self.cache[i], self.scales[i])
         return self.cache[i]
 
     def reserve(self, n):

@@ -105,8 +105,8 @@ def serialize_engine(engine, save_path):
     m = engine._model
     cfg = engine._config
     common = {"format": FORMAT, "tp_size": int(getattr(m, "tp", 1)), "dtype": str(m.dtype).replace("torch.", ""),
-              "kv_block_size": cfg.kv_block_size, "weight_quant": getattr(m, "weight_quant", None)
-              or getattr(m, "_weight_quant", None)}
+              "kv_block_size": cfg.kv_block_size, "kv_cache_dtype": cfg.kv_cache_dtype,
+              "weight_quant": getattr(m, "weight_quant", None) or getattr(m, "_weight_quant", None)}
     rank = int(getattr(m, "tp_rank", 0))
     if isinstance(m, RaggedDecoder):
         named = {k: v for k, v in m.w.items() if k != "layers"}
@@ -144,7 +144,8 @@ def build_engine_from_ds_checkpoint(path, engine_config=None, debug_level=None):
     if desc.get("format") != FORMAT:
         raise ValueError(f"{path}: unknown serialization format {desc.get('format')!r}")
     tp = int(desc["tp_size"])
-    cfg = engine_config or RaggedInferenceEngineConfig(kv_block_size=desc.get("kv_block_size", 64))
+    cfg = engine_config or RaggedInferenceEngineConfig(kv_block_size=desc.get("kv_block_size", 64),
+                                                       kv_cache_dtype=desc.get("kv_cache_dtype"))
     cfg.tensor_parallel = {"tp_size": tp}
     group = _tp_group(tp) if tp > 1 else None
     rank = dist.get_rank(group) if tp > 1 else 0

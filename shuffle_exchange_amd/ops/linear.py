@@ -101,7 +101,10 @@ def fused_rms_rope_linear(x, residual, norm_weight, eps, weight, rope, positions
     """Decode (<= 4 rows) QKV projection in ONE launch: residual + RMSNorm prologue, GEMM, and the
     RoPE + paged-KV-append epilogue (skinny_gemm.hip ``skinny_gemm_pro_rope``; head dim 128).
     Returns (qkv with q / k rotated, h) -- the rotated k and v are already in ``cache`` -- or None
-    when not covered (the caller runs fused_rms_linear + rope_kv_cache_append)."""
+    when not covered (the caller runs fused_rms_linear + rope_kv_cache_append). An FP8 cache
+    (``FP8KVLayer``) is not covered: the epilogue writes bf16 rows."""
+    if not torch.is_tensor(cache):
+        return None
     wk = _rms_operands(x, residual, norm_weight, weight)
     if (wk is None or rope.cos.shape[-1] != 64 or not cache.is_contiguous() or cache.dim() != 5
             or cache.shape[-1] != 128 or wk[0].shape[0] != (nq + 2 * nkv) * 128):

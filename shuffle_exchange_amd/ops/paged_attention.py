@@ -5,13 +5,48 @@ Cache layout per layer: ``[num_blocks, 2, n_kv_heads, block_size, head_dim]`` (b
 (``slot = block_id * block_size + offset``); ``paged_attention`` runs causal attention of the new
 tokens of each sequence over all of its cached keys. Both have PyTorch reference implementations
 (CPU processes / numerics oracles).
+
+FP8 cache (``FP8KVLayer``): ``codes`` in the same index order as the bf16 cache, OCP e4m3fn, plus
+``scales`` ``[num_blocks, 2, n_kv_heads, block_size]`` fp32, one per cached (k|v, kv head, token) row:
+``s = max|row| / 448`` (1 for an all-zero row), ``code = e4m3fn(row / s)`` round-to-nearest-even,
+saturating; dequantisation is ``float(code) * s``. A row is quantised once, when it is appended.
+Every op below takes either cache; ``quantize_kv_fp8`` / ``dequantize_kv_fp8`` are the definition.
 """
 import math
 import os
+from typing import NamedTuple
 
 import torch
 
 from . import native
+
+FP8_MAX = 448.0  # largest finite e4m3fn value
+
+
+class FP8KVLayer(NamedTuple):
+    """One layer of an FP8 paged KV cache."""
+    codes: torch.Tensor   # [num_blocks, 2, nkv, bs, D] float8_e4m3fn
+    scales: torch.Tensor  # [num_blocks, 2, nkv, bs] fp32
+
+
+def quantize_kv_fp8(x):
+    """Rows ``x[..., D]`` -> (codes ``[..., D]`` float8_e4m3fn, scales ``[...]`` fp32)."""
+    x = x.float()
+    amax = x.abs().amax(-1)
+    s = torch.where(amax > 0, amax / FP8_MAX, torch.ones_like(amax))
+    codes = (x / s.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn)
+    return codes, s
+
+
+def dequantize_kv_fp8(layer):
+    """``FP8KVLayer`` -> fp32 ``[blocks, 2, nkv, bs, D]``."""
+    return layer.codes.float() * layer.scales.unsqueeze(-1)
+
+
+def _cache_dims(cache):
+    """(nkv, block_size) of a bf16 cache tensor or an FP8KVLayer."""
+    shape = cache.codes.shape if isinstance(cache, FP8KVLayer) else cache.shape
+    return shape[2], shape[3]
 
 
 def rope_kv_cache_append(qkv, rope, positions, cache, slots, nq, nkv):
@@ -21,8 +56,12 @@ def rope_kv_cache_append(qkv, rope, positions, cache, slots, nq, nkv):
     from .rope import apply_rope_tokens_
     if (native.use_hip(qkv) and qkv.dtype == torch.bfloat16 and qkv.shape[-1] in (64, 128, 256)
             and qkv.is_contiguous() and rope.cos.shape[-1] * 2 == qkv.shape[-1]):
-        torch.ops.sxe.rope_kv_cache_append(qkv, rope.cos, rope.sin, positions.reshape(-1).contiguous().long(), cache,
-                                           slots, int(nq), int(nkv))
+        pos = positions.reshape(-1).contiguous().long()
+        if isinstance(cache, FP8KVLayer):
+            torch.ops.sxe.rope_kv_cache_append_fp8(qkv, rope.cos, rope.sin, pos, cache.codes, cache.scales,
+                                                   slots.contiguous(), int(nq), int(nkv))
+        else:
+            torch.ops.sxe.rope_kv_cache_append(qkv, rope.cos, rope.sin, pos, cache, slots, int(nq), int(nkv))
         return qkv
     apply_rope_tokens_(qkv, rope, nq + nkv, positions)
     kv_cache_append(qkv, cache, slots, nq, nkv)
@@ -30,11 +69,17 @@ def rope_kv_cache_append(qkv, rope, positions, cache, slots, nq, nkv):
 
 
 def kv_cache_append(qkv, cache, slots, nq, nkv):
-    """qkv: [T, nq + 2 nkv, D]; cache: [blocks, 2, nkv, bs, D]; slots: int64 [T] (-1 = skip)."""
-    if native.use_hip(qkv) and qkv.shape[-1] in (64, 128) and qkv.is_contiguous():
+    """qkv: [T, nq + 2 nkv, D]; cache: [blocks, 2, nkv, bs, D] or an FP8KVLayer; slots: int64 [T]
+    (-1 = skip). An FP8 layer quantises the rows (rounded to bf16 first) as they are appended."""
+    fp8 = isinstance(cache, FP8KVLayer)
+    if fp8 and native.use_hip(qkv) and qkv.dtype == torch.bfloat16 and qkv.shape[-1] in (64, 128, 256) \
+            and qkv.is_contiguous():
+        torch.ops.sxe.kv_cache_append_fp8(qkv, cache.codes, cache.scales, slots.contiguous(), int(nq), int(nkv))
+        return
+    if not fp8 and native.use_hip(qkv) and qkv.shape[-1] in (64, 128) and qkv.is_contiguous():
         torch.ops.sxe.kv_cache_append(qkv, cache, slots, int(nq), int(nkv))
         return
-    bs = cache.shape[3]
+    bs = _cache_dims(cache)[1]
     ok = slots >= 0
     if not bool(ok.any()):
         return
@@ -42,15 +87,24 @@ def kv_cache_append(qkv, cache, slots, nq, nkv):
     blk, off = s // bs, s % bs
     k = qkv[ok, nq:nq + nkv]
     v = qkv[ok, nq + nkv:nq + 2 * nkv]
+    if fp8:
+        for kv, rows in enumerate((k, v)):
+            codes, scales = quantize_kv_fp8(rows.to(torch.bfloat16))
+            cache.codes[blk, kv, :, off] = codes
+            cache.scales[blk, kv, :, off] = scales
+        return
     cache[blk, 0, :, off] = k.to(cache.dtype)
     cache[blk, 1, :, off] = v.to(cache.dtype)
 
 
 def _gather_kv(cache, block_row, kv_len):
-    bs = cache.shape[3]
+    bs = _cache_dims(cache)[1]
     nb = (kv_len + bs - 1) // bs
     blocks = block_row[:nb].long()
-    kv = cache[blocks]  # [nb, 2, nkv, bs, D]
+    if isinstance(cache, FP8KVLayer):  # dequantise the sequence's blocks only
+        kv = dequantize_kv_fp8(FP8KVLayer(cache.codes[blocks], cache.scales[blocks]))
+    else:
+        kv = cache[blocks]  # [nb, 2, nkv, bs, D]
     k = kv[:, 0].permute(1, 0, 2, 3).reshape(kv.shape[2], nb * bs, -1)[:, :kv_len]
     v = kv[:, 1].permute(1, 0, 2, 3).reshape(kv.shape[2], nb * bs, -1)[:, :kv_len]
     return k, v  # [nkv, kv_len, D]
@@ -58,7 +112,7 @@ def _gather_kv(cache, block_row, kv_len):
 
 def paged_attention_reference(q, cache, block_table, q_start, q_len, kv_len, scale, window=None):
     T, nq, D = q.shape
-    nkv = cache.shape[2]
+    nkv = _cache_dims(cache)[0]
     G = nq // nkv
     out = torch.zeros(T, nq, D, dtype=q.dtype, device=q.device)
     for s in range(block_table.shape[0]):
@@ -106,9 +160,14 @@ def paged_attention_parts(q, cache, block_table, q_start, q_len, kv_len, scale, 
     partials [splits, T, nq, D] / [splits, T, nq, 2] for a consumer that merges them in its own
     prologue (``ops.linear.fused_merge_linear``: the o_proj skinny GEMM)."""
     if splits is None:
-        splits = choose_splits(block_table.shape[0], cache.shape[2], max_kv_len)
-    out, po, pml = torch.ops.sxe.paged_attention_parts(q, cache, block_table, q_start, q_len, kv_len, float(scale),
-                                                       int(max_kv_len), int(splits), 0)
+        splits = choose_splits(block_table.shape[0], _cache_dims(cache)[0], max_kv_len)
+    if isinstance(cache, FP8KVLayer):
+        out, po, pml = torch.ops.sxe.paged_attention_parts_fp8(q, cache.codes, cache.scales, block_table, q_start,
+                                                               q_len, kv_len, float(scale), int(max_kv_len),
+                                                               int(splits), 0)
+    else:
+        out, po, pml = torch.ops.sxe.paged_attention_parts(q, cache, block_table, q_start, q_len, kv_len,
+                                                           float(scale), int(max_kv_len), int(splits), 0)
     return (out, None) if po.numel() == 0 else (None, (po, pml))
 
 
@@ -151,10 +210,14 @@ def paged_attention(q, cache, block_table, q_start, q_len, kv_len, scale, max_kv
     if window is not None and max_kv_len <= window:
         window = None
     if native.use_hip(q) and q.shape[-1] in (64, 128, 256):
+        nkv = _cache_dims(cache)[0]
         if splits is None:
-            splits = choose_splits(block_table.shape[0], cache.shape[2], max_kv_len)
+            splits = choose_splits(block_table.shape[0], nkv, max_kv_len)
+        if isinstance(cache, FP8KVLayer):  # (the in-kernel split merge is a bf16-cache experiment)
+            return torch.ops.sxe.paged_attention_fp8(q, cache.codes, cache.scales, block_table, q_start, q_len, kv_len,
+                                                     float(scale), int(max_kv_len), int(splits), int(window or 0))
         S = block_table.shape[0]
-        cnt = (_split_counters(q.device, S * cache.shape[2])
+        cnt = (_split_counters(q.device, S * nkv)
                if PA_LAST_MERGE and splits > 1 and q.shape[0] <= 4 * S else None)
         return torch.ops.sxe.paged_attention(q, cache, block_table, q_start, q_len, kv_len, float(scale),
                                              int(max_kv_len), int(splits), int(window or 0), cnt)
