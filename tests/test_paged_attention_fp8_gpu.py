@@ -168,6 +168,57 @@ def test_paged_attention_parts_fp8():
     _check(c, merged)
 
 
+@functools.lru_cache(maxsize=None)
+def _exact_case(nq, nkv, D, bs, seqs=((37, 1), (130, 3), (0, 20))):
+    """A cache that both formats hold exactly: random e4m3 codes (the two NaN codes replaced), code
+    0x7e (= 448) once in every row so that every row scale is exactly 1, and one all-zero row in the
+    history of the second sequence. Its bf16 image is what the bf16 kernel reads."""
+    from shuffle_exchange_amd.ops.paged_attention import FP8KVLayer, dequantize_kv_fp8, quantize_kv_fp8
+    g = torch.Generator(device="cuda").manual_seed(D + bs)
+    nblk = [(c + n + bs - 1) // bs for c, n in seqs]
+    bt = torch.zeros(len(seqs), max(nblk), dtype=torch.int32)
+    perm = torch.randperm(sum(nblk) + 2, generator=torch.Generator().manual_seed(bs)).tolist()
+    for i, nb in enumerate(nblk):
+        bt[i, :nb] = torch.tensor([perm.pop() for _ in range(nb)], dtype=torch.int32)
+    codes = torch.randint(0, 256, (sum(nblk) + 2, 2, nkv, bs, D), device="cuda", generator=g, dtype=torch.uint8)
+    codes[(codes & 0x7f) == 0x7f] = 0x38  # NaN -> 1.0
+    top = torch.randint(0, D, codes.shape[:-1] + (1,), device="cuda", generator=g)
+    codes.scatter_(-1, top, torch.full_like(top, 0x7e, dtype=torch.uint8))
+    codes[int(bt[1, 65 // bs]), :, 0, 65 % bs] = 0
+    layer = FP8KVLayer(codes.view(torch.float8_e4m3fn), torch.ones(codes.shape[:-1], device="cuda"))
+    image = layer.codes.to(torch.bfloat16)
+    qc, qscales = quantize_kv_fp8(image)
+    assert torch.equal(qc.view(torch.uint8), codes) and bool((qscales == 1).all())
+    assert torch.equal(image.float(), dequantize_kv_fp8(layer))
+    i32 = lambda x: torch.tensor(x, dtype=torch.int32, device="cuda")
+    q_len = [n for _, n in seqs]
+    q_start = [sum(q_len[:i]) for i in range(len(seqs))]
+    kv_len = [c + n for c, n in seqs]
+    # |k| reaches 448: small queries keep the softmax spread over many keys
+    q = (torch.randn(sum(q_len), nq, D, device="cuda", generator=g) / 64).to(torch.bfloat16)
+    return dict(q=q, layer=layer, image=image, meta=(bt.cuda(), i32(q_start), i32(q_len), i32(kv_len)),
+                scale=D ** -0.5, maxkv=max(kv_len))
+
+
+@pytest.mark.parametrize("window", [None, 50])
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("nq,nkv,D,bs", [(4, 2, 64, 16), (8, 2, 128, 64), (4, 2, 256, 32)])
+def test_fp8_and_bf16_caches_share_one_kernel_body(nq, nkv, D, bs, splits, window):
+    """With unit row scales the FP8 path does the bf16 path's arithmetic on the bf16 path's values
+    (the widened codes are the bf16 image, and multiplying by 1.0f is exact), so the two outputs agree
+    bit for bit: every head dim, a partial last chunk, several 16-row passes, window chunk skipping,
+    and the partials with the merge launch. Before the two kernels were built from one body the
+    outputs were also bit-equal (worst absolute difference 0 over these 12 cases)."""
+    from shuffle_exchange_amd.ops.paged_attention import paged_attention
+    c = _exact_case(nq, nkv, D, bs)
+    out8 = paged_attention(c["q"], c["layer"], *c["meta"], c["scale"], c["maxkv"], splits, window=window)
+    out16 = paged_attention(c["q"], c["image"], *c["meta"], c["scale"], c["maxkv"], splits, window=window)
+    diff = (out8.float() - out16.float()).abs().max().item()
+    print(f"worst |fp8 - bf16| {diff:.3e}; largest |out| {out16.float().abs().max().item():.3e}")
+    assert bool(out16.float().abs().sum() > 0)
+    assert torch.equal(out8, out16), diff
+
+
 def test_fp8_ops_reject_wrong_operands():
     c = _case(((37, 1), (500, 1), (0, 5)), 8, 2, 128, 64)
     bt, qs, ql, kl = c["meta"]
