@@ -161,6 +161,18 @@ __device__ __forceinline__ int band_qhi(const Band& bd, int b, int S, int j) {
   return max(min(bd.qhi[(int64_t)b * S + j], S - 1), j);
 }
 
+// Ragged (variable-length) forward: q / k / v / o are [T, H, D] token buffers holding sequences back to
+// back, and an int32 work table [N, 3] lists one (first row, length, query block) entry per workgroup
+// and head -- the query blocks are aligned to their sequence's first row, not to multiples of 128 of
+// the buffer. Entries are clamped on read (first row to [0, T - 1], length to [1, T - first row], block
+// to the sequence's last) and every address derives from the clamped values. `window` >= 1: query i of
+// a sequence sees its keys max(0, i - window + 1) .. i (the host passes 2^30 for "no window"); the bound
+// is computed from the sequence-local index, there are no per-token bounds arrays.
+struct Varlen {
+  const int* table;
+  int T, window;
+};
+
 // Heavy-first mapping of the flat block index onto (b, head, row-block) for the causal triangle.
 __device__ __forceinline__ void map_block(int nblk, int BH, bool heavy_last_index, int& bh, int& blk) {
   const int idx = blockIdx.x;
@@ -185,8 +197,11 @@ __device__ __forceinline__ unsigned lds_addr(const char* p) {
   return __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem +
                                         (unsigned)(p - smem));
 }
-template <int ROWS, int D, int NWV = NW>
-__device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t row_stride, int row0, char* lds) {
+// CLAMP (varlen forward): rows past `rmax` re-read row `rmax`, so no row beyond a sequence's last is
+// ever fetched (the tail mask drops their scores; their V rows are finite copies, never junk)
+template <int ROWS, int D, int NWV = NW, bool CLAMP = false>
+__device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t row_stride, int row0, char* lds,
+                                          int rmax = 0) {
   constexpr int CH = D / 8, RPK = 64 / CH;  // rows per 1 KiB wave-instruction
   static_assert(ROWS % (RPK * NWV) == 0, "tile rows must split evenly over the waves");
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -196,7 +211,8 @@ __device__ __forceinline__ void tile_glds(const unsigned short* base, int64_t ro
     const int row = RPK * n + lane / CH;
     const int cpos = lane % CH;
     const int ch = cpos ^ ((((row & 3) << 2) | ((row >> 2) & 3)) & (CH >= 16 ? 15 : CH - 1));
-    glds16_m0(base + (int64_t)(row0 + row) * row_stride + ch * 8, lds_addr(lds + n * 1024));
+    const int grow = CLAMP ? min(row0 + row, rmax) : row0 + row;
+    glds16_m0(base + (int64_t)grow * row_stride + ch * 8, lds_addr(lds + n * 1024));
   }
 }
 
@@ -307,12 +323,17 @@ constexpr int fwd_min_waves() { return D >= 256 ? 1 : 8 / NWF; }
 // The body is shared by fwd_kernel (dense / sparse) and fwd_band_kernel (BAND: the tile walk starts at
 // the first tile the workgroup's first row sees, a wave skips the tiles wholly below its first row's
 // klo, and tiles that the klo of its last row cuts take the masked body with one more compare).
-template <bool SPARSE, int NWF, int D, bool DMA, bool BAND>
+// VARLEN (fwd_varlen_kernel, always with BAND and DMA): the workgroup takes its sequence and query block
+// from the work table; the sequence is then one batch row of length Sq = Sk = kvlen = its length. Q, K
+// and V rows past the sequence's last re-read that last row (no row at or beyond T is touched: an
+// unwritten V row with NaN bits would poison P V even under a zero weight), keys past it fall to the
+// tail mask, query rows past it are computed and not stored, and no LSE is written.
+template <bool SPARSE, int NWF, int D, bool DMA, bool BAND, bool VARLEN = false>
 __device__ __forceinline__ void fwd_body(
     const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
     const unsigned short* __restrict__ v, Strides vs, unsigned short* __restrict__ o, Strides os,
     float* __restrict__ lse, int B, int H, int Hk, int Sq, int Sk, float scale, int causal, Sparse sp, int kvlen,
-    int qoff, Band bd) {
+    int qoff, Band bd, Varlen vl = Varlen{nullptr, 0, 0}) {
   constexpr int ROWB = 2 * D;
   constexpr int BUF = 2 * KT * ROWB;  // one ring slot = K tile + V tile
   int* tlist = reinterpret_cast<int*>(smem + 4 * KT * ROWB) + 1;
@@ -320,7 +341,20 @@ __device__ __forceinline__ void fwd_body(
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
   const int nqb = Sq / QBF;
   int bh, qb;
-  map_block(nqb, B * H, causal != 0, bh, qb);
+  if constexpr (VARLEN) {
+    const int e = blockIdx.x / H;
+    const int* te = vl.table + 3 * (int64_t)e;
+    const int start = min(max(te[0], 0), vl.T - 1);
+    Sq = Sk = kvlen = min(max(te[1], 1), vl.T - start);
+    qb = min(max(te[2], 0), (Sq - 1) / QBF);
+    bh = blockIdx.x - e * H;  // the sequence is batch row 0 of the shifted pointers
+    q += start * qs.s;
+    k += start * ks.s;
+    v += start * vs.s;
+    o += start * os.s;
+  } else {
+    map_block(nqb, B * H, causal != 0, bh, qb);
+  }
   const int b = bh / H, head = bh - b * H;
   const int kh = head / (H / Hk);
   const int q0 = qb * QBF + w * QW;  // this wave's first query
@@ -333,7 +367,8 @@ __device__ __forceinline__ void fwd_body(
   bf16x8 qf[D / 16];
 #pragma unroll
   for (int t = 0; t < D / 16; ++t)
-    qf[t] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)(q0 + r) * qs.s + 16 * t + 8 * h);
+    qf[t] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)(VARLEN ? min(q0 + r, Sq - 1) : q0 + r) * qs.s + 16 * t +
+                                             8 * h);
 
   f32x16 oacc[D / 32];
 #pragma unroll
@@ -344,8 +379,12 @@ __device__ __forceinline__ void fwd_body(
   const int kend = causal ? min(Sk, (qb + 1) * QBF + qoff) : Sk;
   const int nkt = (max(kend, 0) + KT - 1) / KT;
   // band: first tile of the workgroup, this lane's klo and the klo of the wave's first / last row
-  const int tfirst = BAND ? band_klo(bd, b, Sq, qb * QBF) / KT : 0;
-  const int kl = BAND ? band_klo(bd, b, Sq, q0 + r) : 0;
+  auto klo_at = [&](int i) {
+    if constexpr (VARLEN) return max(i - vl.window + 1, 0);
+    else return band_klo(bd, b, Sq, i);
+  };
+  const int tfirst = BAND ? klo_at(qb * QBF) / KT : 0;
+  const int kl = BAND ? klo_at(q0 + r) : 0;
   const int kl_lo = BAND ? __builtin_amdgcn_readfirstlane(kl) : 0;
   const int kl_hi = BAND ? __builtin_amdgcn_readlane(kl, QW - 1) : 0;
   const int ntiles = SPARSE ? build_tile_list(sp, head, 0, nkt, KT, qb * QBF, qb * QBF + QBF, true, tlist)
@@ -356,8 +395,8 @@ __device__ __forceinline__ void fwd_body(
   const int t0 = ntiles > 0 ? tile_at(0) : 0;
   if constexpr (DMA) {
     if (ntiles > 0) {
-      tile_glds<KT, D, NWF>(kp, ks.s, t0 * KT, smem);
-      tile_glds<KT, D, NWF>(vp, vs.s, t0 * KT, smem + KT * ROWB);
+      tile_glds<KT, D, NWF, VARLEN>(kp, ks.s, t0 * KT, smem, Sk - 1);
+      tile_glds<KT, D, NWF, VARLEN>(vp, vs.s, t0 * KT, smem + KT * ROWB, Sk - 1);
     }
     vm_wait_all();
   } else {
@@ -377,8 +416,8 @@ __device__ __forceinline__ void fwd_body(
     const bool more = (t + 1) < ntiles;
     if (more) {
       if constexpr (DMA) {
-        tile_glds<KT, D, NWF>(kp, ks.s, tile_at(t + 1) * KT, smem + (CUR ^ 1) * BUF);
-        tile_glds<KT, D, NWF>(vp, vs.s, tile_at(t + 1) * KT, smem + (CUR ^ 1) * BUF + KT * ROWB);
+        tile_glds<KT, D, NWF, VARLEN>(kp, ks.s, tile_at(t + 1) * KT, smem + (CUR ^ 1) * BUF, Sk - 1);
+        tile_glds<KT, D, NWF, VARLEN>(vp, vs.s, tile_at(t + 1) * KT, smem + (CUR ^ 1) * BUF + KT * ROWB, Sk - 1);
       } else {
         sk.load(kp, ks.s, tile_at(t + 1) * KT, Sk);
         sv.load(vp, vs.s, tile_at(t + 1) * KT, Sk);
@@ -386,7 +425,8 @@ __device__ __forceinline__ void fwd_body(
     }
     const int kbase = tile_at(t) * KT;
     // a wave whose queries all precede this tile has nothing to add (causal)
-    const bool active = (!causal || kbase <= qpos + QW - 1) && !(BAND && kbase + KT - 1 < kl_lo);
+    const bool active = (!causal || kbase <= qpos + QW - 1) && !(BAND && kbase + KT - 1 < kl_lo) &&
+                        !(VARLEN && q0 >= Sq);  // (varlen: a wave wholly past the sequence's end)
     if (active) {
       const char* kt = smem + CUR * BUF;
       const char* vt = kt + KT * ROWB;
@@ -414,6 +454,7 @@ __device__ __forceinline__ void fwd_body(
   const float lt = l + __shfl_xor(l, 32, 64);
   const float inv = lt > 0.f ? 1.f / lt : 0.f;  // a fully masked row outputs zeros
   unsigned short* op = o + b * os.b + head * os.h + (int64_t)(q0 + r) * os.s;
+  if (VARLEN && q0 + r >= Sq) return;  // the last block's overhang: those rows are the next sequence's
 #pragma unroll
   for (int dt = 0; dt < D / 32; ++dt)
 #pragma unroll
@@ -423,6 +464,7 @@ __device__ __forceinline__ void fwd_body(
       for (int e = 0; e < 4; ++e) pk[e] = f32_to_bf16(oacc[dt][4 * rg + e] * inv);
       *reinterpret_cast<u16x4*>(op + 32 * dt + 8 * rg + 4 * h) = pk;
     }
+  if (VARLEN) return;
   if (h == 0) lse[((int64_t)b * H + head) * Sq + q0 + r] = lt > 0.f ? (m + log2f(lt)) * LN2 : INFINITY;
 }
 
@@ -445,6 +487,18 @@ __global__ void __launch_bounds__(NWF * 64, (fwd_min_waves<D, NWF>())) fwd_band_
     float* __restrict__ lse, int B, int H, int Hk, int S, float scale, Band bd) {
   fwd_body<false, NWF, D, true, true>(q, qs, k, ks, v, vs, o, os, lse, B, H, Hk, S, S, scale, 1,
                                       Sparse{nullptr, 0, 0}, S, 0, bd);
+}
+
+// Ragged forward (see Varlen): grid = table entries * H, head fastest, so the query heads of one GQA
+// group read the same K/V tiles at about the same time. One variant per head dim -- 4 waves, LDS-DMA,
+// band walk (no window = a window of 2^30) -- for the compile-time reason given at fwd_band_kernel.
+template <int D>
+__global__ void __launch_bounds__(NW * 64, (fwd_min_waves<D, NW>())) fwd_varlen_kernel(
+    const unsigned short* __restrict__ q, Strides qs, const unsigned short* __restrict__ k, Strides ks,
+    const unsigned short* __restrict__ v, Strides vs, unsigned short* __restrict__ o, Strides os, int H, int Hk,
+    float scale, Varlen vl) {
+  fwd_body<false, NW, D, true, true, true>(q, qs, k, ks, v, vs, o, os, nullptr, 1, H, Hk, 0, 0, scale, 1,
+                                           Sparse{nullptr, 0, 0}, 0, 0, Band{nullptr, nullptr}, vl);
 }
 
 // =============================================================================================
@@ -1367,6 +1421,65 @@ void flash_attn_bwd_band(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor
            band_of(klo, qhi, q, k));
 }
 
+// Causal GQA forward over a ragged token buffer (see fa::Varlen): q [T, Hq, D], k / v [T, Hkv, D], strided
+// views of the packed QKV allowed; table int32 [N, 3] on the device, one (first row, length, query block
+// of 128) row per workgroup and head; window 0 = none. Writes the rows of the table's sequences into
+// `out` (or a fresh [T, Hq, D] tensor whose other rows stay unwritten) and returns it. One launch of
+// N * Hq workgroups, nothing read back on the host.
+template <int D>
+static void fwd_varlen_d(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
+                         const at::Tensor& table, double scale, int window) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds_limit(&fa::fwd_varlen_kernel<D>, 4 * fa::KT * 2 * D);
+    attr = true;
+  }
+  auto st = [](const at::Tensor& t) { return fa::Strides{0, t.stride(0), t.stride(1)}; };
+  const int H = q.size(1), N = table.size(0);
+  hipLaunchKernelGGL(fa::fwd_varlen_kernel<D>, dim3(N * H), dim3(fa::NW * 64), 4 * fa::KT * 2 * D, cur_stream(),
+                     reinterpret_cast<const unsigned short*>(q.data_ptr()), st(q),
+                     reinterpret_cast<const unsigned short*>(k.data_ptr()), st(k),
+                     reinterpret_cast<const unsigned short*>(v.data_ptr()), st(v),
+                     reinterpret_cast<unsigned short*>(o.data_ptr()), st(o), H, (int)k.size(1), (float)scale,
+                     fa::Varlen{table.data_ptr<int>(), (int)q.size(0), window});
+  SXE_LAUNCH_CHECK();
+}
+
+at::Tensor flash_attn_fwd_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor table, double scale,
+                                 int64_t window, c10::optional<at::Tensor> out) {
+  SXE_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "flash_attn varlen: tensors must be [T, H, D]");
+  SXE_CHECK(q.is_cuda() && k.device() == q.device() && v.device() == q.device(), "flash_attn varlen: q/k/v on one GPU");
+  SXE_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
+            "flash_attn varlen: bf16 only");
+  const int64_t T = q.size(0), H = q.size(1), D = q.size(2);
+  SXE_CHECK(D == 64 || D == 128 || D == 256, "flash_attn varlen: head dim must be 64, 128 or 256");
+  SXE_CHECK(k.size(2) == D && v.size(2) == D, "flash_attn varlen: q/k/v head dims differ");
+  SXE_CHECK(k.sizes() == v.sizes() && k.size(0) == T, "flash_attn varlen: q/k/v shapes");
+  SXE_CHECK(k.size(1) >= 1 && H % k.size(1) == 0, "flash_attn varlen: Hq must be a multiple of Hkv");
+  SXE_CHECK(T < (int64_t(1) << 31) / 3, "flash_attn varlen: too many tokens");
+  SXE_CHECK(window >= 0, "flash_attn varlen: window must be >= 0 (0 = none)");
+  SXE_CHECK(table.is_cuda() && table.device() == q.device() && table.scalar_type() == at::kInt && table.dim() == 2 &&
+                table.size(1) == 3 && table.is_contiguous(),
+            "flash_attn varlen: table must be contiguous int32 [N, 3] on the device of q");
+  SXE_CHECK(table.size(0) * H < (int64_t(1) << 31), "flash_attn varlen: table too long");
+  at::Tensor o = out.has_value() && out->defined() ? *out : at::empty({T, H, D}, q.options());
+  SXE_CHECK(o.dim() == 3 && o.sizes() == q.sizes() && o.scalar_type() == at::kBFloat16 && o.device() == q.device(),
+            "flash_attn varlen: out must be bf16 [T, Hq, D] on the device of q");
+  for (const at::Tensor* t : {&q, &k, &v, &o})
+    SXE_CHECK(t->stride(2) == 1 && (t->stride(0) % 8) == 0 && (t->stride(1) % 8) == 0 &&
+                  (reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0,
+              "flash_attn varlen: unit stride on D and 16-byte aligned rows required");
+  if (T == 0 || table.size(0) == 0) return o;
+  c10::DeviceGuard guard(q.device());
+  const int w = window == 0 ? (1 << 30) : (int)std::min<int64_t>(window, 1 << 30);
+  switch (D) {
+    case 64: fwd_varlen_d<64>(q, k, v, o, table, scale, w); break;
+    case 256: fwd_varlen_d<256>(q, k, v, o, table, scale, w); break;
+    default: fwd_varlen_d<128>(q, k, v, o, table, scale, w); break;
+  }
+  return o;
+}
+
 }  // namespace sxe
 
 TORCH_LIBRARY_FRAGMENT(sxe, m) {
@@ -1381,6 +1494,9 @@ TORCH_LIBRARY_FRAGMENT(sxe, m) {
   m.def("flash_attn_fwd_band(Tensor q, Tensor k, Tensor v, Tensor klo, Tensor qhi, float scale) -> Tensor[]");
   m.def("flash_attn_bwd_band(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor(a!) dq, "
         "Tensor(b!) dk, Tensor(c!) dv, Tensor klo, Tensor qhi, float scale) -> ()");
+  // returns `out` itself when it is given (eager inference only: the result then aliases an argument)
+  m.def("flash_attn_fwd_varlen(Tensor q, Tensor k, Tensor v, Tensor table, float scale, int window=0, "
+        "Tensor(a!)? out=None) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(sxe, CUDA, m) {
   m.impl("flash_attn_fwd", &sxe::flash_attn_fwd);
@@ -1389,4 +1505,5 @@ TORCH_LIBRARY_IMPL(sxe, CUDA, m) {
   m.impl("flash_attn_bwd_sparse", &sxe::flash_attn_bwd_sparse);
   m.impl("flash_attn_fwd_band", &sxe::flash_attn_fwd_band);
   m.impl("flash_attn_bwd_band", &sxe::flash_attn_bwd_band);
+  m.impl("flash_attn_fwd_varlen", &sxe::flash_attn_fwd_varlen);
 }

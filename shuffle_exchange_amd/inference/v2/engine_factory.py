@@ -23,7 +23,7 @@ def build_hf_engine(path_or_model, engine_config: RaggedInferenceEngineConfig = 
         from .engine_v2 import _tp_group
         tp_group = _tp_group(tp)
     model = load_hf_decoder(path_or_model, dtype=dtype, device=device, weight_quant=weight_quant, tp_group=tp_group,
-                            tp_size=tp)
+                            tp_size=tp, pins=engine_config.implementations if engine_config is not None else None)
     return InferenceEngineV2(model, engine_config)
 
 

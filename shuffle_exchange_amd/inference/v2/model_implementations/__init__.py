@@ -23,7 +23,7 @@ def ragged_model_for(model, weight_quant=None, tp_group=None, tp_size=1, pins=No
         dtype = p.dtype if p.dtype in (__import__("torch").bfloat16, __import__("torch").float16,
                                        __import__("torch").float32) else None
         return load_hf_decoder(model, dtype=dtype, device=p.device, weight_quant=weight_quant, tp_group=tp_group,
-                               tp_size=tp_size)
+                               tp_size=tp_size, pins=pins)
     if hasattr(model, "layers") and hasattr(model.layers[0], "self_attn") and hasattr(model, "embed_tokens"):
         return RaggedLlama(model, weight_quant=weight_quant, tp_group=tp_group, tp_size=tp_size, pins=pins)
     raise NotImplementedError(f"no ragged inference implementation for {type(model).__name__}")

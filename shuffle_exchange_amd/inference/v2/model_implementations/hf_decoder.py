@@ -339,9 +339,13 @@ def convert_hf_weights(spec, sd, hf_cfg=None):
 
 
 # ---------------------------------------------------------------------------- shared attention
-def ragged_attention(qkv, kv_layer, batch, nq, nkv, D, scale, window=None):
+def ragged_attention(qkv, kv_layer, batch, nq, nkv, D, scale, window=None, impl=None):
     """Attention of a ragged batch's new tokens over their paged KV: pure prefills of >= 128 tokens
-    run the training flash kernel (MFMA, causal), the rest the paged-attention kernel."""
+    run the training flash kernel (MFMA, causal), the rest the paged-attention kernel. ``impl``: the
+    pinned attention implementation; ``dense_blocked_attention_varlen_prefill`` runs all fresh prompts
+    in one variable-length flash launch instead (modules/implementations.py)."""
+    if getattr(impl, "varlen_prefill", False):
+        return impl(qkv, kv_layer, batch, nq, nkv, scale, window=window)
     q = qkv[:, :nq]
     use_flash = (native.use_hip(qkv) and D == 128 and qkv.dtype == torch.bfloat16 and
                  (window is None or batch.max_kv_len <= window))
@@ -506,11 +510,19 @@ class RaggedDecoder:
     device / vocab_size / forward(batch, kv_cache) -> last-token fp32 logits)."""
 
     QUANT_KEYS = ("qkv_w", "o_w", "gu_w", "down_w", "fc1_w", "fc2_w", "sh_gu", "sh_down")
+    attn_impl = None  # class default: a decoder rebuilt by serialization.py (no __init__) is unpinned
 
     def __init__(self, spec: DecoderSpec, weights, dtype=torch.bfloat16, device=None, weight_quant=None,
-                 tp_group=None, tp_size=1):
+                 tp_group=None, tp_size=1, pins=None):
         self.spec = spec
         device = torch.device(device) if device is not None else torch.device("cpu")
+        # a pinned attention implementation (RaggedInferenceEngineConfig.implementations); unpinned, the
+        # choice between flash and paged prefill is ragged_attention's own
+        self.attn_impl, self._pins = None, pins
+        if (pins or {}).get("attention"):
+            from ..modules import heuristics as H
+            self.attn_impl = H.instantiate_attention(
+                H.AttentionConfig(spec.head_dim, spec.nq, spec.nkv, dtype, spec.sliding_window or 0, device.type), pins)
         from .... import comm as dist
         self.tp, self.tp_group = int(tp_size), tp_group  # tp_group None with tp_size > 1: the world
         self.tp_rank = dist.get_rank(tp_group) if self.tp > 1 else 0
@@ -586,7 +598,7 @@ class RaggedDecoder:
             apply_rope_tokens_(qkv, self.rope, nq + nkv, batch.positions, rot_dim=s.rotary_dim)
         kv_layer = kv_cache.layer(li)
         kv_cache_append(qkv, kv_layer, batch.slots, nq, nkv)
-        o = ragged_attention(qkv, kv_layer, batch, nq, nkv, D, self.scale, s.sliding_window)
+        o = ragged_attention(qkv, kv_layer, batch, nq, nkv, D, self.scale, s.sliding_window, self.attn_impl)
         if self.tp == 1:
             return linear(o.reshape(T, nq * D), L["o_w"], L.get("o_b"))
         y = linear(o.reshape(T, nq * D), L["o_w"])
@@ -649,7 +661,8 @@ class RaggedDecoder:
         return logits
 
 
-def load_hf_decoder(model_or_path, dtype=torch.bfloat16, device=None, weight_quant=None, tp_group=None, tp_size=1):
+def load_hf_decoder(model_or_path, dtype=torch.bfloat16, device=None, weight_quant=None, tp_group=None, tp_size=1,
+                    pins=None):
     """A transformers model instance or a local checkpoint directory (config.json + safetensors /
     pytorch_model*.bin, loaded without executing pickled code) -> RaggedDecoder (this rank's
     tensor-parallel shard when ``tp_size > 1``)."""
@@ -662,4 +675,4 @@ def load_hf_decoder(model_or_path, dtype=torch.bfloat16, device=None, weight_qua
         sd = {k: v.detach() for k, v in model_or_path.state_dict().items()}
     spec = spec_from_hf_config(cfg)
     return RaggedDecoder(spec, convert_hf_weights(spec, sd, cfg), dtype=dtype, device=device, weight_quant=weight_quant,
-                         tp_group=tp_group, tp_size=tp_size)
+                         tp_group=tp_group, tp_size=tp_size, pins=pins)

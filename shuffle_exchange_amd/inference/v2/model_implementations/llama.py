@@ -8,7 +8,9 @@ BLAS linear, cutlass MoE GEMM) replaced by this framework's gfx950 kernels:
   * RMSNorm with fused residual add (norm.hip), projections through hipBLASLt,
   * RoPE in place on the packed QKV (rope.hip), KV scatter into the blocked cache and paged
     attention (paged_attn.hip); sequences in pure prefill (no history, >= 128 new tokens) run the
-    training flash-attention kernel instead (MFMA, causal; their padding rows are discarded),
+    training flash-attention kernel instead (MFMA, causal; their padding rows are discarded); with
+    the pinned ``dense_blocked_attention_varlen_prefill`` implementation all of them share one launch
+    of the variable-length flash kernel on the packed QKV (modules/implementations.py),
   * SwiGLU (act.hip); Mixtral experts via the grouped MoE path of moe/,
   * only the last token of every sequence goes through the final norm + LM head.
 The weights are the training modules' own parameters (no copy): a trained LlamaForCausalLM /
@@ -167,6 +169,8 @@ class RaggedLlama:
     def _attention(self, qkv, kv_layer, batch):
         nq, D = self.nq, self.head_dim
         scale = D ** -0.5
+        if getattr(self.attn_impl, "varlen_prefill", False):  # one flash launch + one paged launch
+            return self.attn_impl(qkv, kv_layer, batch, nq, self.nkv, scale)
         q = qkv[:, :nq]
         use_flash = native.use_hip(qkv) and self.attn_impl.flash_prefill and D == 128 and qkv.dtype == torch.bfloat16
         flash_ids = [i for i in range(batch.num_seqs)

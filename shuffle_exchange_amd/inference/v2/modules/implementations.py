@@ -126,6 +126,43 @@ class PagedAttention:
         self.cfg = cfg
 
 
+@register("attention", "dense_blocked_attention_varlen_prefill", priority=-10)
+class PagedAttentionVarlenPrefill:
+    """Fresh prompts of at least VARLEN_PREFILL_MIN tokens run together in ONE launch of the
+    variable-length flash kernel (flash_attn.hip ``flash_attn_fwd_varlen``, reading the packed QKV
+    in place: head dims 64 / 128 / 256, any sliding window); decode tokens, continuation chunks and
+    shorter prompts run in one launch of the paged kernel. The launch count per layer does not
+    depend on the number of sequences. Selected only by a pin (lowest priority)."""
+    flash_prefill = False
+    flash_min_tokens = 1 << 30
+    varlen_prefill = True
+
+    @staticmethod
+    def supports(cfg):
+        return _hip(cfg) and cfg.dtype == torch.bfloat16 and cfg.head_dim in (64, 128, 256)
+
+    def __init__(self, cfg):
+        self.cfg = cfg
+
+    def __call__(self, qkv, kv_layer, batch, nq, nkv, scale, window=None):
+        """qkv [T, nq + 2 nkv, D] after RoPE, its k / v already appended to ``kv_layer``; ``batch``: a
+        RaggedBatch (ragged.py builds the work table and the paged subset once per batch). The two
+        kernels write disjoint rows of one buffer: the paged launch allocates it and the flash launch
+        fills the routed sequences' rows in place, so nothing is gathered or copied."""
+        from ....ops.attention import varlen_attention
+        from ....ops.paged_attention import paged_attention
+        q = qkv[:, :nq]
+        table = getattr(batch, "varlen_table", None)
+        if table is None or table.shape[0] == 0:  # nothing routed (or a decode-graph batch)
+            return paged_attention(q, kv_layer, batch.block_table, batch.q_start, batch.q_len, batch.kv_len, scale,
+                                   batch.max_kv_len, window=window)
+        out = None
+        if batch.rest_ids:
+            out = paged_attention(q, kv_layer, batch.rest_block_table, batch.rest_q_start, batch.rest_q_len,
+                                  batch.rest_kv_len, scale, batch.rest_max_kv_len, window=window)
+        return varlen_attention(q, qkv[:, nq:nq + nkv], qkv[:, nq + nkv:], table, scale, window=window, out=out)
+
+
 # ----------------------------------------------------------------------------------------- moe
 @register("moe", "hip_topk_grouped", priority=10)
 class HipTopKMoE:

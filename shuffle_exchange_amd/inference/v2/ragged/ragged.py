@@ -156,25 +156,62 @@ class DSStateManager:
             self.kv.free(s.blocks)
 
 
+VARLEN_QB = 128  # query rows per workgroup of flash_attn_fwd_varlen (fa::QB in csrc/kernels/flash_attn.hip)
+# Fresh prompts of at least this many tokens take the variable-length flash kernel under the
+# dense_blocked_attention_varlen_prefill implementation; shorter ones stay on the paged kernel. It
+# started at 128, the threshold of the per-sequence flash path (FLASH_PREFILL_MIN). Measured on MI355X
+# with 32 fresh prompts, Llama-3-8B heads (tools/varlen_prefill_bench.py --short,
+# profiles/varlen_prefill_bench.log), varlen / paged time per layer: 0.16 at 127 tokens, 0.18 at 96,
+# 0.19 at 64, 0.30 at 32, 0.57 at 16 -- no crossover down to 16 tokens, the shortest measured, so the
+# threshold sits there; below it nothing is measured and the paged kernel stays.
+VARLEN_PREFILL_MIN = 16
+
+
+def build_varlen_table(q_start, q_len, seen, min_len=None, qb=VARLEN_QB):
+    """Work table of flash_attn_fwd_varlen for one ragged batch, from per-sequence host lists: a
+    sequence is routed when it has no history (``seen == 0``) and at least ``min_len`` new tokens
+    (default VARLEN_PREFILL_MIN), and contributes one ``(first row, length, query block)`` entry per
+    block of ``qb`` query rows, ceil(len / qb) in all. Entries are ordered heavy first (a later block
+    of a causal sequence walks more keys). Returns ``(routed ids, rest ids, entries)``."""
+    min_len = VARLEN_PREFILL_MIN if min_len is None else min_len
+    routed = [i for i in range(len(q_len)) if seen[i] == 0 and q_len[i] >= max(1, min_len)]
+    rset = set(routed)
+    rest = [i for i in range(len(q_len)) if i not in rset]
+    rows = [(q_start[i], q_len[i], b) for i in routed for b in range(-(-q_len[i] // qb))]
+    rows.sort(key=lambda e: -e[2])
+    return routed, rest, rows
+
+
 class RaggedBatch:
     """Device metadata of one forward over a ragged set of sequences (all int tensors on device).
 
     input_ids [T]; positions [T] (absolute); slots [T] (cache slot of every new token);
     q_start / q_len / kv_len [S] int32; block_table [S, max_blocks] int32; last_idx [S] int64.
     Host copies of the small per-sequence ints are kept for scheduling decisions.
+
+    For the variable-length prefill (built once here, in the same pinned buffer and copy, so the
+    layers do no host work): ``varlen_table`` int32 [N, 3] (``build_varlen_table``) over the routed
+    sequences ``varlen_ids``, and the paged-attention metadata of the others ``rest_ids``:
+    ``rest_q_start`` / ``rest_q_len`` / ``rest_kv_len`` [R], ``rest_block_table`` [R, max_blocks],
+    ``rest_max_kv_len``. The two kernels write disjoint rows of one output, which stands in for a
+    per-token routed mask.
     """
 
-    def __init__(self, seqs, tokens, block_size, device):
+    def __init__(self, seqs, tokens, block_size, device, varlen_min=None):
         S = len(seqs)
         lens = [int(t.numel()) for t in tokens]
         T = sum(lens)
         maxb = max(1, max(len(s.blocks) for s in seqs))
+        starts = [sum(lens[:i]) for i in range(S)]
+        routed, rest, rows = build_varlen_table(starts, lens, [s.seen_tokens for s in seqs], varlen_min)
+        N, R = len(rows), (len(rest) if routed else 0)  # nothing routed: the "rest" is the whole batch
+        base = 3 * S + S * maxb
         i64 = torch.empty(3 * T + S, dtype=torch.int64, pin_memory=torch.cuda.is_available() and device.type == "cuda")
-        i32 = torch.zeros(3 * S + S * maxb, dtype=torch.int32,
+        i32 = torch.zeros(base + 3 * N + 3 * R + R * maxb, dtype=torch.int32,
                           pin_memory=torch.cuda.is_available() and device.type == "cuda")
         ids, pos, slots, last = i64[:T], i64[T:2 * T], i64[2 * T:3 * T], i64[3 * T:]
         qs, ql, kl = i32[:S], i32[S:2 * S], i32[2 * S:3 * S]
-        bt = i32[3 * S:].view(S, maxb)
+        bt = i32[3 * S:base].view(S, maxb)
         t = 0
         self.host_q_len, self.host_kv_len, self.host_seen = [], [], []
         for i, (s, tk) in enumerate(zip(seqs, tokens)):
@@ -191,11 +228,29 @@ class RaggedBatch:
             self.host_kv_len.append(s.seen_tokens + n)
             self.host_seen.append(s.seen_tokens)
             t += n
+        if N:
+            i32[base:base + 3 * N] = torch.tensor(rows, dtype=torch.int32).reshape(-1)
+        if R:
+            ridx = torch.tensor(rest)
+            r0 = base + 3 * N
+            for j, src in enumerate((qs, ql, kl)):
+                i32[r0 + j * R:r0 + (j + 1) * R] = src[ridx]
+            i32[r0 + 3 * R:] = bt[ridx].reshape(-1)
         d64 = i64.to(device, non_blocking=True)
         d32 = i32.to(device, non_blocking=True)
         self.input_ids, self.positions, self.slots, self.last_idx = d64[:T], d64[T:2 * T], d64[2 * T:3 * T], d64[3 * T:]
         self.q_start, self.q_len, self.kv_len = d32[:S], d32[S:2 * S], d32[2 * S:3 * S]
-        self.block_table = d32[3 * S:].view(S, maxb)
+        self.block_table = d32[3 * S:base].view(S, maxb)
         self.num_tokens, self.num_seqs = T, S
         self.max_kv_len = max(self.host_kv_len) if S else 0
-        self.host_q_start = [sum(lens[:i]) for i in range(S)]
+        self.host_q_start = starts
+        self.varlen_ids, self.rest_ids, self.host_varlen_table = routed, rest, rows
+        self.varlen_table = d32[base:base + 3 * N].view(N, 3)
+        if routed:
+            r0 = base + 3 * N
+            self.rest_q_start, self.rest_q_len, self.rest_kv_len = (d32[r0 + j * R:r0 + (j + 1) * R] for j in range(3))
+            self.rest_block_table = d32[r0 + 3 * R:].view(R, maxb)
+            self.rest_max_kv_len = max((self.host_kv_len[i] for i in rest), default=0)
+        else:
+            self.rest_q_start, self.rest_q_len, self.rest_kv_len = self.q_start, self.q_len, self.kv_len
+            self.rest_block_table, self.rest_max_kv_len = self.block_table, self.max_kv_len

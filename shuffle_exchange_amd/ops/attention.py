@@ -22,6 +22,10 @@ causal mask to keys ``klo[b, i] <= j <= i``. On the GPU the band variants of the
 of eight equal documents costs about an eighth of the causal work. Padded shapes append the pad
 tokens as one trailing document; CPU and uncovered cases build the boolean mask and call SDPA.
 
+``varlen_attention`` is the inference prefill entry point over a ragged token buffer [T, H, D] (whole
+sequences back to back, any lengths, optional sliding window): one ``flash_attn_fwd_varlen`` launch
+driven by a small device work table, forward only.
+
 ``attention_qkv_rope`` is the training entry point of the Llama family: it takes the fused QKV
 projection output [B, S, Hq + 2*Hkv, D], applies RoPE in place, runs attention reading q/k/v as
 strided views, and in backward writes dq/dk/dv straight into ONE dqkv buffer (then rotates the
@@ -489,6 +493,44 @@ def attention_with_lse(q, k, v, causal=True, softmax_scale=None):
         _, _, _, o, lse = _padded_fwd(q, k, v, causal, scale)
         return o[:, :Sq, :, :D].to(q.dtype), lse[:, :, :Sq].contiguous()
     return reference_attention(q, k, v, causal, scale, return_lse=True)
+
+
+def varlen_hip_supported(q, k, v, out=None):
+    """``flash_attn_fwd_varlen`` runs these [T, H, D] tensors in place."""
+    if os.environ.get("SXE_ATTN_BACKEND") == "sdpa" or not native.use_hip(q):
+        return False
+    ts = (q, k, v) if out is None else (q, k, v, out)
+    return (q.dim() == 3 and q.shape[-1] in HEAD_DIMS and k.shape[-1] == q.shape[-1] and v.shape[-1] == q.shape[-1]
+            and k.shape[1] > 0 and q.shape[1] % k.shape[1] == 0
+            and all(t.dtype == torch.bfloat16 and t.stride(2) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+                    and (t.storage_offset() * t.element_size()) % 16 == 0 for t in ts))
+
+
+def varlen_attention(q, k, v, table, scale=None, window=None, out=None):
+    """Causal GQA attention of whole sequences packed in a ragged token buffer: q [T, Hq, D], k / v
+    [T, Hkv, D] (strided views of the packed QKV allowed); ``table`` int32 [N, 3] lists one (first row,
+    length, query block of 128) row per query block of every sequence to run
+    (inference/v2/ragged/ragged.py ``build_varlen_table``). ``window=W``: query i of a sequence sees
+    its keys max(0, i - W + 1) .. i. Rows of the table's sequences are written into ``out`` (default: a
+    new [T, Hq, D] tensor) and every other row is left as it was; returns ``out``. On the GPU this is
+    one launch of ``flash_attn_fwd_varlen`` with no host synchronisation; CPU tensors and cases the
+    kernel does not cover run ``reference_attention`` per sequence (this reads the table on the host)."""
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if window is not None and int(window) < 1:
+        raise ValueError(f"window must be >= 1, got {window}")
+    if q.is_cuda:
+        native.require_hip()
+        if varlen_hip_supported(q, k, v, out):
+            return torch.ops.sxe.flash_attn_fwd_varlen(q, k, v, table, float(scale), int(window or 0), out)
+        warning_once(f"sxe varlen attention: HIP kernel does not cover dtype={q.dtype} D={q.shape[-1]} "
+                     f"strides={q.stride()}; using the per-sequence reference")
+    if out is None:
+        out = torch.zeros_like(q)
+    for s, n in dict.fromkeys((int(r[0]), int(r[1])) for r in table.tolist()):
+        sl = slice(s, s + n)
+        bounds = band_bounds(n, 1, q.device, window=window) if window is not None and window < n else None
+        out[sl] = reference_attention(q[sl][None], k[sl][None], v[sl][None], True, scale, bounds=bounds)[0]
+    return out
 
 
 def reference_attention(q, k, v, causal=True, scale=None, return_lse=False, bounds=None):

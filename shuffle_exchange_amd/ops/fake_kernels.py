@@ -90,6 +90,11 @@ def _fa_bwd_band(dout, q, k, v, o, lse, dq, dk, dv, klo, qhi, scale):
     return None
 
 
+@_reg("sxe::flash_attn_fwd_varlen")
+def _fa_fwd_varlen(q, k, v, table, scale, window=0, out=None):
+    return torch.empty_like(q, memory_format=torch.contiguous_format)
+
+
 @_reg("sxe::xent_fwd")
 def _xent_fwd(logits, target, ignore_index, inplace_grad, scale, grad_scale):
     r = logits.shape[0]
