@@ -123,9 +123,10 @@ at::Tensor gated_act_fwd(at::Tensor gu, int64_t act) {
 at::Tensor gated_act_bwd(at::Tensor dout, at::Tensor gu, int64_t act) {
   SXE_CHECK(gu.is_contiguous() && dout.is_contiguous(), "gated_act_bwd: contiguous");
   const int64_t two_i = gu.size(-1);
+  SXE_CHECK(two_i % 16 == 0, "gated_act_bwd: inner size must be a multiple of 16");
   const int I = (int)(two_i / 2);
   const int64_t rows = gu.numel() / two_i;
-  SXE_CHECK(dout.numel() == rows * I, "gated_act_bwd: shape");
+  SXE_CHECK(dout.numel() == rows * I && dout.scalar_type() == gu.scalar_type(), "gated_act_bwd: shape");
   c10::DeviceGuard guard(gu.device());
   auto dgu = at::empty_like(gu);
   if (rows == 0) return dgu;
@@ -379,8 +380,11 @@ at::Tensor bias_act_fwd(at::Tensor x, c10::optional<at::Tensor> bias, int64_t ac
 
 at::Tensor bias_act_bwd(at::Tensor dy, at::Tensor x, c10::optional<at::Tensor> bias, int64_t act) {
   SXE_CHECK(x.is_contiguous() && dy.is_contiguous() && dy.sizes() == x.sizes(), "bias_act_bwd: shapes");
+  SXE_CHECK(x.numel() % 8 == 0 && dy.scalar_type() == x.scalar_type(), "bias_act_bwd: numel % 8 == 0, dy dtype");
   const int C = (int)x.size(-1);
+  SXE_CHECK(C % 8 == 0, "bias_act_bwd: channels % 8");
   const bool hb = bias.has_value() && bias->defined();
+  if (hb) SXE_CHECK(bias->numel() == C && bias->scalar_type() == x.scalar_type(), "bias_act_bwd: bias");
   c10::DeviceGuard guard(x.device());
   auto dx = at::empty_like(x);
   const int64_t n = x.numel();

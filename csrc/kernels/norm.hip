@@ -261,18 +261,23 @@ static int pick_nch(int H) {
     case 4: { constexpr int NAME = 4; __VA_ARGS__; break; }   \
     case 8: { constexpr int NAME = 8; __VA_ARGS__; break; }   \
     case 16: { constexpr int NAME = 16; __VA_ARGS__; break; } \
-    default: TORCH_CHECK(false, "sxe norm: hidden size too large (max 16384)"); \
+    default: TORCH_CHECK(false, "sxe norm: no kernel for this hidden size"); \
   }
 
+// One wave holds a whole row in registers, at most 16 chunks of 512 elements: H <= 8192. The
+// block-per-row forward (rows <= 256) spreads a row over 4 waves and reaches 16384.
+constexpr int kNormMaxH = 8192, kNormMaxHBlock = 16384, kNormBlockRows = 256;
 
 // Returns (y, rstd, mean_or_empty, h_or_empty).
 std::vector<at::Tensor> norm_fwd(at::Tensor x, c10::optional<at::Tensor> residual, at::Tensor weight,
                                  c10::optional<at::Tensor> bias, double eps, bool layernorm) {
   SXE_CHECK(x.is_contiguous() && weight.is_contiguous(), "norm_fwd: contiguous inputs");
   const int H = (int)x.size(-1);
-  SXE_CHECK(H % 8 == 0 && H <= 16384, "norm_fwd: hidden size must be a multiple of 8 and <= 16384");
+  SXE_CHECK(H > 0 && H % 8 == 0, "norm_fwd: hidden size must be a multiple of 8, got ", H);
   SXE_CHECK(weight.numel() == H, "norm_fwd: weight size");
   const int64_t rows = x.numel() / H;
+  SXE_CHECK(H <= kNormMaxH || (H <= kNormMaxHBlock && rows <= kNormBlockRows),
+            "norm_fwd: hidden size must be <= 8192 (<= 16384 with at most 256 rows), got ", H, " with ", rows, " rows");
   c10::DeviceGuard guard(x.device());
   auto y = at::empty_like(x);
   auto rstd = at::empty({rows}, x.options().dtype(at::kFloat));
@@ -286,7 +291,7 @@ std::vector<at::Tensor> norm_fwd(at::Tensor x, c10::optional<at::Tensor> residua
   if (has_b) SXE_CHECK(bias->scalar_type() == weight.scalar_type() && bias->numel() == H, "norm_fwd: bias");
   if (rows == 0) return {y, rstd, mean, h};
   // few rows (decode, small batches): a whole block per row; otherwise one wave per row
-  const bool block_rows = rows <= 256 && H >= 1024;
+  const bool block_rows = rows <= kNormBlockRows && H >= 1024;
   const int grid = block_rows ? (int)rows : (int)std::min<int64_t>((rows + 3) / 4, 2048);
   DT d = dtype_of(x);
   const int nch = block_rows ? pick_nch((H + 3) / 4) : pick_nch(H);
@@ -310,6 +315,8 @@ std::vector<at::Tensor> norm_bwd(at::Tensor dy, at::Tensor x, at::Tensor rstd, c
                                  at::Tensor weight, c10::optional<at::Tensor> dres, bool layernorm) {
   SXE_CHECK(dy.is_contiguous() && x.is_contiguous() && weight.is_contiguous(), "norm_bwd: contiguous");
   const int H = (int)x.size(-1);
+  SXE_CHECK(H > 0 && H % 8 == 0 && H <= kNormMaxH, "norm_bwd: hidden size must be a multiple of 8 and <= 8192, got ", H);
+  SXE_CHECK(weight.numel() == H, "norm_bwd: weight size");
   const int64_t rows = x.numel() / H;
   SXE_CHECK(dy.sizes() == x.sizes(), "norm_bwd: dy shape");
   c10::DeviceGuard guard(x.device());
@@ -317,6 +324,7 @@ std::vector<at::Tensor> norm_bwd(at::Tensor dy, at::Tensor x, at::Tensor rstd, c
   const bool has_dres = dres.has_value() && dres->defined();
   if (has_dres) SXE_CHECK(dres->sizes() == x.sizes() && dres->is_contiguous() && dres->scalar_type() == x.scalar_type(), "norm_bwd: dres");
   const bool wf32 = weight.scalar_type() == at::kFloat;
+  SXE_CHECK(wf32 || weight.scalar_type() == x.scalar_type(), "norm_bwd: weight dtype must be fp32 or match x");
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((rows + 3) / 4, 512));
   auto dw_part = at::empty({grid, H}, x.options().dtype(at::kFloat));
   auto db_part = layernorm ? at::empty({grid, H}, x.options().dtype(at::kFloat)) : at::empty({0}, x.options().dtype(at::kFloat));

@@ -66,6 +66,8 @@ void rope_(at::Tensor x, at::Tensor cos_t, at::Tensor sin_t, c10::optional<at::T
   const int64_t head_stride = x.stride(-2);
   const int64_t tok_stride = x.stride(-3);
   const int64_t tokens = x.numel() / ((int64_t)nheads * D);
+  // every access is a 16-byte vector at t * tok_stride + h * head_stride + 8 * k
+  SXE_CHECK(tokens <= 1 || tok_stride % 8 == 0, "rope_: token stride must be a multiple of 8 elements (16-byte vectors)");
   // tokens must be uniformly strided across the leading dims ([B, S] flattened).
   if (x.dim() > 3 && x.size(-4) > 1)
     SXE_CHECK(x.stride(-4) == tok_stride * x.size(-3), "rope_: leading dims must flatten uniformly");

@@ -30,6 +30,9 @@ __device__ __forceinline__ float row_lse(const typename dt_traits<T>::storage* _
       float lm = v[0];
 #pragma unroll
       for (int j = 1; j < 8; ++j) lm = fmaxf(lm, v[j]);
+      // an all -inf chunk (masked vocabulary padding, banned tokens) holds no mass: v - lm would be
+      // -inf - -inf = NaN, and NaN * exp(-inf) survives the merge once the lane has a finite max
+      if (lm == -INFINITY) continue;
       float ls = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) ls += __expf(v[j] - lm);

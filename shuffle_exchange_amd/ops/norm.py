@@ -64,9 +64,22 @@ class _NormFn(torch.autograd.Function):
         return dx, (dx if ctx.has_res else None), dw, db, None, None
 
 
+def _kernel_ok(x, *params):
+    """The HIP kernels hold a row in one wave's registers: hidden a multiple of 8, at most 8192. The
+    forward alone also takes up to 16384 when there are at most 256 rows (a block per row); every
+    other size runs the torch path below."""
+    H = x.shape[-1]
+    if H == 0 or H % 8:
+        return False
+    if H <= 8192:
+        return True
+    needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x,) + params)
+    return H <= 16384 and x.numel() // H <= 256 and not needs_grad
+
+
 def rms_norm(x, weight, eps=1e-6, residual=None):
     """Returns y (and the new residual h = x + residual when ``residual`` is given)."""
-    if native.use_hip(x):
+    if native.use_hip(x) and _kernel_ok(x, weight, residual):
         y, h = _NormFn.apply(x, residual, weight, None, eps, False)
         return (y, h) if residual is not None else y
     h = x + residual if residual is not None else x
@@ -75,7 +88,7 @@ def rms_norm(x, weight, eps=1e-6, residual=None):
 
 
 def layer_norm(x, weight, bias=None, eps=1e-5, residual=None):
-    if native.use_hip(x):
+    if native.use_hip(x) and _kernel_ok(x, weight, bias, residual):
         y, h = _NormFn.apply(x, residual, weight, bias, eps, True)
         return (y, h) if residual is not None else y
     h = x + residual if residual is not None else x
