@@ -12,6 +12,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/core/DeviceGuard.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define SXE_CHECK(cond, ...) TORCH_CHECK(cond, "sxe: ", __VA_ARGS__)
 #define SXE_CHECK_CUDA(t) SXE_CHECK((t).is_cuda(), #t " must be a GPU tensor")
@@ -140,6 +141,30 @@ inline int stream_grid(int64_t work_items, int block) {
 }
 
 inline hipStream_t cur_stream() { return at::hip::getCurrentHIPStream().stream(); }
+
+// Dynamic LDS a launch may ask for (gfx950 has 160 KiB per CU).
+constexpr size_t kMaxDynamicLds = 144 * 1024;
+
+// Call before launching `Kernel` with dynamic LDS: the first call per instantiation raises the
+// kernel's limit (64 KiB by default) to kMaxDynamicLds.
+template <auto Kernel>
+inline void allow_max_dynamic_lds() {
+  static const bool done = [] {
+    SXE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds));
+    return true;
+  }();
+  (void)done;
+}
+
+// f(std::integral_constant<int, D>) for a head dim the attention kernels are built for
+template <class F>
+inline void dispatch_head_dim(int D, const char* op, F&& f) {
+  if (D == 128) f(std::integral_constant<int, 128>{});
+  else if (D == 64) f(std::integral_constant<int, 64>{});
+  else if (D == 256) f(std::integral_constant<int, 256>{});
+  else SXE_CHECK(false, op, ": head_dim must be 64, 128 or 256");
+}
 
 }  // namespace sxe
 

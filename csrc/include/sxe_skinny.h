@@ -56,20 +56,9 @@ inline int pick_nw(int tiles, int ss_total, int min_ss, int wg8_per_cu) {
 constexpr int kNoRoundCap = 1024 / kNumCUs;
 static_assert(kNumCUs * kNoRoundCap * 4 >= 4096, "kNoRoundCap must not bind");
 
-// ---- host: dynamic LDS ----------------------------------------------------------------------------
-constexpr size_t kMaxDynamicLds = 144 * 1024;
-
-// Call before launching `Kernel` with dynamic LDS: the first call per instantiation raises the
-// kernel's limit (64 KiB by default) to kMaxDynamicLds.
-template <auto Kernel>
-inline void allow_max_dynamic_lds() {
-  static const bool done = [] {
-    SXE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)kMaxDynamicLds));
-    return true;
-  }();
-  (void)done;
-}
+// ---- host: dynamic LDS (sxe_common.h) -------------------------------------------------------------
+using sxe::allow_max_dynamic_lds;
+using sxe::kMaxDynamicLds;
 
 // ---- device: the cross-wave reduce ----------------------------------------------------------------
 // After `red[wave][lane] = acc; __syncthreads();`: the sum of the NW waves' partial tiles, for wave 0.

@@ -994,22 +994,29 @@ __global__ void __launch_bounds__(256) dkdv_reduce_kernel(const float* __restric
 static fa::Strides strides_of(const at::Tensor& t) {
   return fa::Strides{t.stride(0), t.stride(1), t.stride(2)};
 }
+static unsigned short* u16(const at::Tensor& t) { return reinterpret_cast<unsigned short*>(t.data_ptr()); }
+
+// What the kernels' 16-byte loads and stores need of each of `ts` ([.., D], at least 2-D): bf16,
+// unit stride on D, every other stride and the base address a multiple of 16 bytes
+static void check_bf16_rows(std::initializer_list<const at::Tensor*> ts, const char* op) {
+  for (const at::Tensor* t : ts) {
+    bool ok = t->scalar_type() == at::kBFloat16 && t->stride(-1) == 1 &&
+              (reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0;
+    for (int64_t i = 0; i + 1 < t->dim(); ++i) ok = ok && t->stride(i) % 8 == 0;
+    SXE_CHECK(ok, op, ": bf16 with unit stride on D and 16-byte aligned rows required");
+  }
+}
 
 // q: [B, Sq, Hq, D]; k, v: [B, Sk, Hk, D]; D in {64, 128, 256}; Sq, Sk multiples of 128
 static void check_qkv(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v) {
   SXE_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, "flash_attn: tensors must be [B, S, H, D]");
-  SXE_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
-            "flash_attn: bf16 only");
+  check_bf16_rows({&q, &k, &v}, "flash_attn");
   const int64_t D = q.size(3);
   SXE_CHECK(D == 64 || D == 128 || D == 256, "flash_attn: head dim must be 64, 128 or 256");
   SXE_CHECK(k.size(3) == D && v.size(3) == D, "flash_attn: q/k/v head dims differ");
-  SXE_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1, "flash_attn: unit stride on D");
   SXE_CHECK(k.sizes() == v.sizes() && q.size(0) == k.size(0), "flash_attn: q/k/v shapes");
   SXE_CHECK(q.size(2) % k.size(2) == 0, "flash_attn: Hq must be a multiple of Hkv");
   SXE_CHECK(q.size(1) % fa::QB == 0 && k.size(1) % fa::QB == 0, "flash_attn: seq lengths must be multiples of 128");
-  for (const at::Tensor* t : {&q, &k, &v})
-    SXE_CHECK((t->stride(1) % 8) == 0 && (t->stride(2) % 8) == 0 && (t->stride(0) % 8) == 0 &&
-                  (reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0, "flash_attn: 16-byte aligned rows required");
 }
 
 static fa::Sparse sparse_of(const c10::optional<at::Tensor>& layout, int64_t block, const at::Tensor& q) {
@@ -1041,104 +1048,37 @@ static int env_int(const char* name, int dflt) {
   const char* e = std::getenv(name);
   return (e != nullptr && *e != 0) ? std::atoi(e) : dflt;
 }
-// 4-wave forward workgroups only when forced (SXE_FA_FWD_WAVES=4): 8 waves are equal or faster on
-// every measured shape -- causal equal at head dims 64 / 128, non-causal 3-7 % faster
-// (profiles/r05/attn_fwd_waves_ab.log, attn_fwd_waves_d64_ab.log; one earlier box showed 4 waves
-// 6 % ahead at D64 causal, which a second box did not reproduce)
-static bool fwd_narrow(int D) {
-  (void)D;
-  return env_int("SXE_FA_FWD_WAVES", 8) == 4;
-}
-static bool fwd_dma() { return env_int("SXE_FA_FWD_DMA", 1) != 0; }
 
-template <typename F>
-static void set_lds_limit(F* f, size_t bytes) {
-  SXE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)bytes));
-}
+// Dynamic LDS of the forward, dQ and varlen kernels: the K/V tile ring (sparse mode adds kListBytes)
+template <int D> constexpr size_t kRingBytes = 4 * fa::KT * 2 * D;
 
-// kv_len: valid keys (the rest of the padded key axis is masked); qoff: causal offset (query i sees
-// keys <= i + qoff), default Sk - Sq (bottom-right aligned)
-template <int D>
-static std::vector<at::Tensor> fwd_impl_d(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
-                                          fa::Sparse sp, int kvlen, int qoff, fa::Band bd) {
-  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1), Hk = k.size(2);
-  auto o = at::empty({B, Sq, H, D}, q.options());
-  auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
-  constexpr int ROWB = 2 * D;
-  const size_t lds = 4 * fa::KT * ROWB + (sp.layout ? kListBytes : 0);
-  static bool attr = false;
-  if (!attr) {
-    const size_t mx = 4 * fa::KT * ROWB + kListBytes;
-    set_lds_limit(&fa::fwd_kernel<false, 4, D>, mx);
-    set_lds_limit(&fa::fwd_kernel<true, 4, D>, mx);
-    if constexpr (D < 256) {
-      set_lds_limit(&fa::fwd_kernel<false, 8, D>, mx);
-      set_lds_limit(&fa::fwd_kernel<true, 8, D>, mx);
-      set_lds_limit(&fa::fwd_kernel<false, 4, D, true>, mx);
-      set_lds_limit(&fa::fwd_kernel<true, 4, D, true>, mx);
-      set_lds_limit(&fa::fwd_kernel<false, 8, D, true>, mx);
-      set_lds_limit(&fa::fwd_kernel<true, 8, D, true>, mx);
-      set_lds_limit(&fa::fwd_band_kernel<8, D>, mx);
-    }
-    set_lds_limit(&fa::fwd_band_kernel<4, D>, mx);
-    attr = true;
-  }
-  // 8 waves share each staged K/V tile when the query axis allows; head dim 256 runs 4 (register budget)
-  const bool wide = D < 256 && Sq % 256 == 0 && !fwd_narrow(D);
-  const int grid = (Sq / fa::QB) * B * H;
-  auto launch = [&](auto kern, int nwf) {
-    hipLaunchKernelGGL(kern, dim3(nwf == 8 ? grid / 2 : grid), dim3(nwf * 64), lds, cur_stream(),
-                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                       reinterpret_cast<unsigned short*>(o.data_ptr()), strides_of(o), lse.data_ptr<float>(), B, H, Hk,
-                       Sq, Sk, (float)scale, causal ? 1 : 0, sp, kvlen, qoff);
-  };
-  if (bd.klo != nullptr) {  // band mode: always the LDS-DMA forward (see fwd_band_kernel)
-    auto launch_band = [&](auto kern, int nwf) {
-      hipLaunchKernelGGL(kern, dim3(nwf == 8 ? grid / 2 : grid), dim3(nwf * 64), lds, cur_stream(),
-                         reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                         reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                         reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                         reinterpret_cast<unsigned short*>(o.data_ptr()), strides_of(o), lse.data_ptr<float>(), B, H,
-                         Hk, Sq, (float)scale, bd);
-    };
-    if constexpr (D < 256) {
-      if (wide) {
-        launch_band(fa::fwd_band_kernel<8, D>, 8);
-        SXE_LAUNCH_CHECK();
-        return {o, lse};
-      }
-    }
-    launch_band(fa::fwd_band_kernel<4, D>, 4);
-    SXE_LAUNCH_CHECK();
-    return {o, lse};
-  }
-  if constexpr (D < 256) {
-    if (fwd_dma()) {
-      if (wide)
-        sp.layout ? launch(fa::fwd_kernel<true, 8, D, true>, 8) : launch(fa::fwd_kernel<false, 8, D, true>, 8);
-      else
-        sp.layout ? launch(fa::fwd_kernel<true, 4, D, true>, 4) : launch(fa::fwd_kernel<false, 4, D, true>, 4);
-      SXE_LAUNCH_CHECK();
-      return {o, lse};
-    }
-    if (wide) {
-      sp.layout ? launch(fa::fwd_kernel<true, 8, D>, 8) : launch(fa::fwd_kernel<false, 8, D>, 8);
-      SXE_LAUNCH_CHECK();
-      return {o, lse};
-    }
-  }
-  sp.layout ? launch(fa::fwd_kernel<true, 4, D>, 4) : launch(fa::fwd_kernel<false, 4, D>, 4);
+// Compile-time tags that carry a kernel or a variant parameter through the generic launch lambdas
+template <auto Kernel> using kern_t = std::integral_constant<decltype(Kernel), Kernel>;
+template <int N> using int_t = std::integral_constant<int, N>;
+
+// Every flash kernel starts here: opt `Kernel` into more than 64 KiB of dynamic LDS (the first call
+// per instantiation), launch it on the current stream, check.
+template <auto Kernel, typename... Args>
+static void launch(int grid, int waves, size_t lds, Args... args) {
+  allow_max_dynamic_lds<Kernel>();
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(waves * 64), lds, cur_stream(), args...);
   SXE_LAUNCH_CHECK();
-  return {o, lse};
 }
 
-static std::vector<at::Tensor> fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
-                                        fa::Sparse sp, int64_t kv_len = -1, int64_t causal_offset = INT64_MIN,
-                                        fa::Band bd = fa::Band{nullptr, nullptr}) {
-  check_qkv(q, k, v);
+// The mask of one call. kvlen: valid keys (the rest of the padded key axis is masked); qoff: causal
+// offset (query i sees keys <= i + qoff), default Sk - Sq (bottom-right aligned); sp.layout / bd.klo
+// are null unless the call is block-sparse / banded.
+struct Mask {
+  bool causal;
+  int kvlen, qoff;
+  fa::Sparse sp;
+  fa::Band bd;
+};
+constexpr fa::Sparse kNoSparse{nullptr, 0, 0};
+constexpr fa::Band kNoBand{nullptr, nullptr};
+
+static Mask mask_of(const at::Tensor& q, const at::Tensor& k, bool causal, fa::Sparse sp, int64_t kv_len,
+                    int64_t causal_offset, fa::Band bd) {
   const int Sq = q.size(1), Sk = k.size(1);
   const int kvlen = kv_len < 0 ? Sk : (int)kv_len;
   SXE_CHECK(kvlen >= 1 && kvlen <= Sk, "flash_attn: kv_len must be in [1, Sk]");
@@ -1146,104 +1086,102 @@ static std::vector<at::Tensor> fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v
   SXE_CHECK(!sp.layout || (Sq == Sk && qoff == 0), "block-sparse attention needs Sq == Sk");
   SXE_CHECK(!bd.klo || (causal && Sq == Sk && qoff == 0 && kvlen == Sk && !sp.layout),
             "flash_attn band: needs causal, Sq == Sk, causal offset 0, no kv_len and no sparse layout");
-  c10::DeviceGuard guard(q.device());
-  switch (q.size(3)) {
-    case 64: return fwd_impl_d<64>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
-    case 256: return fwd_impl_d<256>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
-    default: return fwd_impl_d<128>(q, k, v, causal, scale, sp, kvlen, qoff, bd);
-  }
+  return Mask{causal, kvlen, qoff, sp, bd};
 }
 
 template <int D>
-static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
-                       at::Tensor dq, at::Tensor dk, at::Tensor dv, bool causal, double scale, fa::Sparse sp,
-                       int kvlen, int qoff, fa::Band bd) {
+static std::vector<at::Tensor> fwd_impl_d(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, double scale,
+                                          const Mask& m) {
+  static_assert(kRingBytes<D> + kListBytes <= kMaxDynamicLds, "forward LDS exceeds the opt-in limit");
   const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1), Hk = k.size(2);
-  constexpr int ROWB = 2 * D;
+  auto o = at::empty({B, Sq, H, D}, q.options());
+  auto lse = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
+  const size_t lds = kRingBytes<D> + (m.sp.layout ? kListBytes : 0);
+  const int grid = (Sq / fa::QB) * B * H;
+  // one variant: NWF waves per workgroup, K/V staged by LDS-DMA or through registers
+  auto run = [&](auto nwf, auto dma) {
+    constexpr int NWF = decltype(nwf)::value;
+    constexpr bool DMA = decltype(dma)::value;
+    auto go = [&](auto kern, auto... tail) {
+      launch<decltype(kern)::value>(NWF == 8 ? grid / 2 : grid, NWF, lds, u16(q), strides_of(q), u16(k), strides_of(k),
+                                    u16(v), strides_of(v), u16(o), strides_of(o), lse.data_ptr<float>(), B, H, Hk, Sq,
+                                    tail...);
+    };
+    auto dense = [&](auto kern) { go(kern, Sk, (float)scale, m.causal ? 1 : 0, m.sp, m.kvlen, m.qoff); };
+    if (m.bd.klo != nullptr) go(kern_t<fa::fwd_band_kernel<NWF, D>>{}, (float)scale, m.bd);  // always LDS-DMA
+    else if (m.sp.layout != nullptr) dense(kern_t<fa::fwd_kernel<true, NWF, D, DMA>>{});
+    else dense(kern_t<fa::fwd_kernel<false, NWF, D, DMA>>{});
+  };
+  if constexpr (D < 256) {
+    // 8 waves share each staged K/V tile when the query axis allows. 4-wave workgroups only when
+    // forced (SXE_FA_FWD_WAVES=4): 8 waves are equal or faster on every measured shape -- causal
+    // equal at head dims 64 / 128, non-causal 3-7 % faster (profiles/r05/attn_fwd_waves_ab.log,
+    // attn_fwd_waves_d64_ab.log; one earlier box showed 4 waves 6 % ahead at D64 causal, which a
+    // second box did not reproduce)
+    const bool wide = Sq % 256 == 0 && env_int("SXE_FA_FWD_WAVES", 8) != 4;
+    const bool dma = m.bd.klo != nullptr || env_int("SXE_FA_FWD_DMA", 1) != 0;
+    if (wide) dma ? run(int_t<8>{}, std::true_type{}) : run(int_t<8>{}, std::false_type{});
+    else dma ? run(int_t<4>{}, std::true_type{}) : run(int_t<4>{}, std::false_type{});
+  } else {
+    run(int_t<4>{}, std::true_type{});  // head dim 256: 4 waves (register budget), LDS-DMA only
+  }
+  return {o, lse};
+}
+
+static std::vector<at::Tensor> fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
+                                        fa::Sparse sp, int64_t kv_len = -1, int64_t causal_offset = INT64_MIN,
+                                        fa::Band bd = kNoBand) {
+  check_qkv(q, k, v);
+  const Mask m = mask_of(q, k, causal, sp, kv_len, causal_offset, bd);
+  c10::DeviceGuard guard(q.device());
+  std::vector<at::Tensor> out;
+  dispatch_head_dim(q.size(3), "flash_attn", [&](auto d) { out = fwd_impl_d<decltype(d)::value>(q, k, v, scale, m); });
+  return out;
+}
+
+template <int D>
+static void bwd_impl_d(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                       const at::Tensor& o, const at::Tensor& lse, const at::Tensor& dq, const at::Tensor& dk,
+                       const at::Tensor& dv, double scale, const Mask& m) {
   using G_ = fa::KVL<D>;
+  constexpr int KB8 = D == 128 ? 256 : fa::QB;  // keys per dK/dV workgroup in its widest (8-wave) form
+  static_assert(kRingBytes<D> + kListBytes <= kMaxDynamicLds, "dQ LDS exceeds the opt-in limit");
+  static_assert(fa::KVL<D, KB8>::VBLK + 2 * G_::SLOT + kListBytes <= kMaxDynamicLds,
+                "dK/dV LDS exceeds the opt-in limit");
+  const bool causal = m.causal;
+  const fa::Sparse sp = m.sp;
+  const int B = q.size(0), Sq = q.size(1), H = q.size(2), Sk = k.size(1), Hk = k.size(2);
   auto ndelta = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
   auto lse2 = at::empty({B, H, Sq}, q.options().dtype(at::kFloat));
   const int64_t rows = (int64_t)B * H * Sq;
   constexpr int RPB = 256 / (D / 8);
-  hipLaunchKernelGGL(fa::delta_kernel<D>, dim3((rows + RPB - 1) / RPB), dim3(256), 0, cur_stream(),
-                     reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                     reinterpret_cast<const unsigned short*>(o.data_ptr()), strides_of(o), lse.data_ptr<float>(),
-                     ndelta.data_ptr<float>(), lse2.data_ptr<float>(), B, H, Sq);
+  hipLaunchKernelGGL(fa::delta_kernel<D>, dim3((rows + RPB - 1) / RPB), dim3(256), 0, cur_stream(), u16(dout),
+                     strides_of(dout), u16(o), strides_of(o), lse.data_ptr<float>(), ndelta.data_ptr<float>(),
+                     lse2.data_ptr<float>(), B, H, Sq);
   SXE_LAUNCH_CHECK();
-  const size_t lds_dq = 4 * fa::KT * ROWB + (sp.layout ? kListBytes : 0);
-  const size_t lds_kv_max = G_::VBLK + 2 * G_::SLOT + kListBytes;
-  static bool attr_set = false;
-  if (!attr_set) {  // > 64 KiB of dynamic LDS must be opted into (gfx950 has 160 KiB per CU)
-    set_lds_limit(&fa::dq_kernel<false, D>, 4 * fa::KT * ROWB + kListBytes);
-    set_lds_limit(&fa::dq_kernel<true, D>, 4 * fa::KT * ROWB + kListBytes);
-    if constexpr (D < 256) {
-      set_lds_limit(&fa::dq_kernel<false, D, 8>, 4 * fa::KT * ROWB + kListBytes);
-      set_lds_limit(&fa::dq_kernel<true, D, 8>, 4 * fa::KT * ROWB + kListBytes);
-    }
-    set_lds_limit(&fa::dkdv_kernel<false, D>, lds_kv_max);
-    set_lds_limit(&fa::dkdv_kernel<true, D>, lds_kv_max);
-    if constexpr (D == 128) {
-      const size_t mx8 = fa::KVL<D, 256>::VBLK + 2 * G_::SLOT + kListBytes;
-      set_lds_limit(&fa::dkdv_kernel<false, D, 3, 8>, mx8);
-      set_lds_limit(&fa::dkdv_kernel<true, D, 3, 8>, mx8);
-    }
-    if constexpr (D >= 256) {
-      set_lds_limit(&fa::dkdv_kernel<false, D, 1>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_kernel<true, D, 1>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_kernel<false, D, 2>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_kernel<true, D, 2>, lds_kv_max);
-    }
-    // band mode: the same variants, dense only
-    set_lds_limit(&fa::dq_band_kernel<D>, 4 * fa::KT * ROWB + kListBytes);
-    if constexpr (D < 256) set_lds_limit(&fa::dq_band_kernel<D, 8>, 4 * fa::KT * ROWB + kListBytes);
-    set_lds_limit(&fa::dkdv_band_kernel<false, D>, lds_kv_max);
-    set_lds_limit(&fa::dkdv_band_kernel<true, D>, lds_kv_max);
-    if constexpr (D == 128) {
-      const size_t mx8 = fa::KVL<D, 256>::VBLK + 2 * G_::SLOT + kListBytes;
-      set_lds_limit(&fa::dkdv_band_kernel<false, D, 3, 8>, mx8);
-      set_lds_limit(&fa::dkdv_band_kernel<true, D, 3, 8>, mx8);
-    }
-    if constexpr (D >= 256) {
-      set_lds_limit(&fa::dkdv_band_kernel<false, D, 1>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_band_kernel<true, D, 1>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_band_kernel<false, D, 2>, lds_kv_max);
-      set_lds_limit(&fa::dkdv_band_kernel<true, D, 2>, lds_kv_max);
-    }
-    attr_set = true;
-  }
+  const size_t lds_dq = kRingBytes<D> + (sp.layout ? kListBytes : 0);
+  auto run_dq = [&](auto nwf) {
+    constexpr int NWF = decltype(nwf)::value;
+    auto go = [&](auto kern, auto... tail) {
+      launch<decltype(kern)::value>((Sq / (NWF * fa::QW)) * B * H, NWF, lds_dq, u16(q), strides_of(q), u16(k),
+                                    strides_of(k), u16(v), strides_of(v), u16(dout), strides_of(dout),
+                                    lse.data_ptr<float>(), ndelta.data_ptr<float>(), u16(dq), strides_of(dq), B, H, Hk,
+                                    Sq, tail...);
+    };
+    auto dense = [&](auto kern) { go(kern, Sk, (float)scale, causal ? 1 : 0, sp, m.kvlen, m.qoff); };
+    if (m.bd.klo != nullptr) go(kern_t<fa::dq_band_kernel<D, NWF>>{}, (float)scale, m.bd);
+    else if (sp.layout != nullptr) dense(kern_t<fa::dq_kernel<true, D, NWF>>{});
+    else dense(kern_t<fa::dq_kernel<false, D, NWF>>{});
+  };
   // 8-wave dQ workgroups from 8k queries on (auto; SXE_FA_DQ_WAVES=4 / 8 forces): 1.5-2 % faster
   // fwd+bwd at S8k / S32k, neutral at 2k (profiles/r05/attn_bwd_waves_ab.log)
   const int dqw = env_int("SXE_FA_DQ_WAVES", 0);
   const bool dq8 = D < 256 && Sq % 256 == 0 && (dqw == 8 || (dqw == 0 && Sq >= 8192));
-  auto* dqk = sp.layout ? fa::dq_kernel<true, D> : fa::dq_kernel<false, D>;
   if constexpr (D < 256) {
-    if (dq8) dqk = sp.layout ? fa::dq_kernel<true, D, 8> : fa::dq_kernel<false, D, 8>;
-  }
-  if (bd.klo != nullptr) {
-    auto* dqb = fa::dq_band_kernel<D>;
-    if constexpr (D < 256) {
-      if (dq8) dqb = fa::dq_band_kernel<D, 8>;
-    }
-    hipLaunchKernelGGL(dqb, dim3((Sq / (dq8 ? 2 * fa::QB : fa::QB)) * B * H), dim3(dq8 ? 512 : 256), lds_dq,
-                       cur_stream(), reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                       lse.data_ptr<float>(), ndelta.data_ptr<float>(),
-                       reinterpret_cast<unsigned short*>(dq.data_ptr()), strides_of(dq), B, H, Hk, Sq, (float)scale,
-                       bd);
+    dq8 ? run_dq(int_t<8>{}) : run_dq(int_t<4>{});
   } else {
-    hipLaunchKernelGGL(dqk, dim3((Sq / (dq8 ? 2 * fa::QB : fa::QB)) * B * H),
-                       dim3(dq8 ? 512 : 256), lds_dq, cur_stream(),
-                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                       lse.data_ptr<float>(), ndelta.data_ptr<float>(),
-                       reinterpret_cast<unsigned short*>(dq.data_ptr()), strides_of(dq), B, H, Hk, Sq, Sk,
-                       (float)scale, causal ? 1 : 0, sp, kvlen, qoff);
+    run_dq(int_t<4>{});
   }
-  SXE_LAUNCH_CHECK();
   // sparse: always one workgroup per query head (per-head tile lists); with GQA the per-head fp32
   // partials are reduced; causal GQA: split to remove the key-block-0 tail (see dkdv_kernel)
   // query heads per dK/dV workgroup in the split form (a divisor of the GQA group; sparse: 1). Auto
@@ -1281,120 +1219,80 @@ static void bwd_impl_d(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v
     pk = at::empty({B, Sk, np, D}, q.options().dtype(at::kFloat));
     pv = at::empty({B, Sk, np, D}, q.options().dtype(at::kFloat));
   }
-  auto launch = [&](auto kern, int heads, int nwk = 4) {
-    hipLaunchKernelGGL(kern, dim3((Sk / (nwk * fa::QW)) * B * heads), dim3(nwk * 64), lds_kv, cur_stream(),
-                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                       lse2.data_ptr<float>(), ndelta.data_ptr<float>(),
-                       reinterpret_cast<unsigned short*>(dk.data_ptr()), strides_of(dk),
-                       reinterpret_cast<unsigned short*>(dv.data_ptr()), strides_of(dv),
-                       partials ? pk.data_ptr<float>() : nullptr, partials ? pv.data_ptr<float>() : nullptr, B, H, Hk,
-                       Sq, Sk, (float)scale, causal ? 1 : 0, sp, qoff, hpw);
-  };
-  auto launch_band = [&](auto kern, int heads, int nwk = 4) {
-    hipLaunchKernelGGL(kern, dim3((Sk / (nwk * fa::QW)) * B * heads), dim3(nwk * 64), lds_kv, cur_stream(),
-                       reinterpret_cast<const unsigned short*>(q.data_ptr()), strides_of(q),
-                       reinterpret_cast<const unsigned short*>(k.data_ptr()), strides_of(k),
-                       reinterpret_cast<const unsigned short*>(v.data_ptr()), strides_of(v),
-                       reinterpret_cast<const unsigned short*>(dout.data_ptr()), strides_of(dout),
-                       lse2.data_ptr<float>(), ndelta.data_ptr<float>(),
-                       reinterpret_cast<unsigned short*>(dk.data_ptr()), strides_of(dk),
-                       reinterpret_cast<unsigned short*>(dv.data_ptr()), strides_of(dv),
-                       partials ? pk.data_ptr<float>() : nullptr, partials ? pv.data_ptr<float>() : nullptr, B, H, Hk,
-                       Sq, (float)scale, hpw, bd);
-  };
-  // the dK/dV launch(es) of one form: SPLIT = one workgroup per query-head group (partials / direct)
-  auto run_dkdv = [&](auto splitc, int heads) {
+  // one dK/dV kernel: SPLIT = one workgroup per query-head group (partials / direct), PART (see
+  // dkdv_tile), NWK waves per workgroup; `heads` = workgroups per key block and batch
+  auto run = [&](auto splitc, auto part, auto nwk, int heads) {
     constexpr bool SP = decltype(splitc)::value;
-    if (bd.klo != nullptr) {  // band mode: the same variant choice
-      if constexpr (D >= 256) {
-        if (!one_sweep) {
-          launch_band(fa::dkdv_band_kernel<SP, D, 1>, heads);
-          SXE_LAUNCH_CHECK();
-          launch_band(fa::dkdv_band_kernel<SP, D, 2>, heads);
-          return;
-        }
-      }
-      if constexpr (D == 128) {
-        if (kv8) {
-          launch_band(fa::dkdv_band_kernel<SP, D, 3, 8>, heads, 8);
-          return;
-        }
-      }
-      launch_band(fa::dkdv_band_kernel<SP, D>, heads);
-      return;
-    }
+    constexpr int PART = decltype(part)::value, NWK = decltype(nwk)::value;
+    auto go = [&](auto kern, auto... tail) {
+      launch<decltype(kern)::value>((Sk / (NWK * fa::QW)) * B * heads, NWK, lds_kv, u16(q), strides_of(q), u16(k),
+                                    strides_of(k), u16(v), strides_of(v), u16(dout), strides_of(dout),
+                                    lse2.data_ptr<float>(), ndelta.data_ptr<float>(), u16(dk), strides_of(dk), u16(dv),
+                                    strides_of(dv), partials ? pk.data_ptr<float>() : nullptr,
+                                    partials ? pv.data_ptr<float>() : nullptr, B, H, Hk, Sq, tail...);
+    };
+    if (m.bd.klo != nullptr) go(kern_t<fa::dkdv_band_kernel<SP, D, PART, NWK>>{}, (float)scale, hpw, m.bd);
+    else go(kern_t<fa::dkdv_kernel<SP, D, PART, NWK>>{}, Sk, (float)scale, causal ? 1 : 0, sp, m.qoff, hpw);
+  };
+  auto run_dkdv = [&](auto splitc, int heads) {
     if constexpr (D >= 256) {
       if (!one_sweep) {
-        launch(fa::dkdv_kernel<SP, D, 1>, heads);
-        SXE_LAUNCH_CHECK();
-        launch(fa::dkdv_kernel<SP, D, 2>, heads);
+        run(splitc, int_t<1>{}, int_t<4>{}, heads);
+        run(splitc, int_t<2>{}, int_t<4>{}, heads);
         return;
       }
     }
     if constexpr (D == 128) {
       if (kv8) {
-        launch(fa::dkdv_kernel<SP, D, 3, 8>, heads, 8);
+        run(splitc, int_t<3>{}, int_t<8>{}, heads);
         return;
       }
     }
-    launch(fa::dkdv_kernel<SP, D>, heads);
+    run(splitc, int_t<3>{}, int_t<4>{}, heads);
   };
   if (split) {
     run_dkdv(std::true_type{}, np);
-    SXE_LAUNCH_CHECK();
     if (partials) {
       const int64_t n8 = (int64_t)B * Sk * Hk * (D / 8);
       hipLaunchKernelGGL(fa::dkdv_reduce_kernel<D>, dim3(stream_grid(n8, 256)), dim3(256), 0, cur_stream(),
-                         pk.data_ptr<float>(), pv.data_ptr<float>(), reinterpret_cast<unsigned short*>(dk.data_ptr()),
-                         strides_of(dk), reinterpret_cast<unsigned short*>(dv.data_ptr()), strides_of(dv), B, Sk, np,
-                         Hk);
+                         pk.data_ptr<float>(), pv.data_ptr<float>(), u16(dk), strides_of(dk), u16(dv), strides_of(dv),
+                         B, Sk, np, Hk);
+      SXE_LAUNCH_CHECK();
     }
   } else {
     run_dkdv(std::false_type{}, Hk);
   }
-  SXE_LAUNCH_CHECK();
 }
 
 // dq/dk/dv are caller-provided (possibly strided views of one dqkv buffer).
 static void bwd_impl(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
                      at::Tensor dq, at::Tensor dk, at::Tensor dv, bool causal, double scale, fa::Sparse sp,
                      int64_t kv_len = -1, int64_t causal_offset = INT64_MIN,
-                     fa::Band bd = fa::Band{nullptr, nullptr}) {
+                     fa::Band bd = kNoBand) {
   check_qkv(q, k, v);
   check_qkv(dq, dk, dv);
-  const int Sq = q.size(1), Sk = k.size(1);
-  const int kvlen = kv_len < 0 ? Sk : (int)kv_len;
-  SXE_CHECK(kvlen >= 1 && kvlen <= Sk, "flash_attn_bwd: kv_len must be in [1, Sk]");
-  const int qoff = causal_offset == INT64_MIN ? Sk - Sq : (int)causal_offset;
+  const Mask m = mask_of(q, k, causal, sp, kv_len, causal_offset, bd);
   SXE_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes() && dout.stride(3) == 1 && o.stride(3) == 1,
             "flash_attn_bwd: dout/o shapes");
   SXE_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() && dv.sizes() == v.sizes(), "flash_attn_bwd: grad shapes");
-  SXE_CHECK(lse.is_contiguous() && lse.size(2) == Sq, "flash_attn_bwd: lse [B, H, Sq]");
-  SXE_CHECK(!bd.klo || (causal && Sq == Sk && qoff == 0 && kvlen == Sk && !sp.layout),
-            "flash_attn_bwd band: needs causal, Sq == Sk, causal offset 0, no kv_len and no sparse layout");
+  SXE_CHECK(lse.is_contiguous() && lse.size(2) == q.size(1), "flash_attn_bwd: lse [B, H, Sq]");
   c10::DeviceGuard guard(q.device());
-  switch (q.size(3)) {
-    case 64: return bwd_impl_d<64>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
-    case 256: return bwd_impl_d<256>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
-    default: return bwd_impl_d<128>(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, sp, kvlen, qoff, bd);
-  }
+  dispatch_head_dim(q.size(3), "flash_attn_bwd", [&](auto d) {
+    bwd_impl_d<decltype(d)::value>(dout, q, k, v, o, lse, dq, dk, dv, scale, m);
+  });
 }
 
 static int64_t offset_arg(int64_t causal_offset) { return causal_offset == -(int64_t(1) << 40) ? INT64_MIN : causal_offset; }
 
 std::vector<at::Tensor> flash_attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v, bool causal, double scale,
                                        int64_t kv_len, int64_t causal_offset) {
-  return fwd_impl(q, k, v, causal, scale, fa::Sparse{nullptr, 0, 0}, kv_len, offset_arg(causal_offset));
+  return fwd_impl(q, k, v, causal, scale, kNoSparse, kv_len, offset_arg(causal_offset));
 }
 
 void flash_attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
                     at::Tensor dq, at::Tensor dk, at::Tensor dv, bool causal, double scale, int64_t kv_len,
                     int64_t causal_offset) {
-  bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, fa::Sparse{nullptr, 0, 0}, kv_len,
-           offset_arg(causal_offset));
+  bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, causal, scale, kNoSparse, kv_len, offset_arg(causal_offset));
 }
 
 std::vector<at::Tensor> flash_attn_fwd_sparse(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor layout,
@@ -1412,13 +1310,12 @@ void flash_attn_bwd_sparse(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tens
 // keys klo[b, i] <= j <= i, and qhi[b, j] is the last query that sees key j.
 std::vector<at::Tensor> flash_attn_fwd_band(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor klo, at::Tensor qhi,
                                             double scale) {
-  return fwd_impl(q, k, v, true, scale, fa::Sparse{nullptr, 0, 0}, -1, INT64_MIN, band_of(klo, qhi, q, k));
+  return fwd_impl(q, k, v, true, scale, kNoSparse, -1, INT64_MIN, band_of(klo, qhi, q, k));
 }
 
 void flash_attn_bwd_band(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor o, at::Tensor lse,
                          at::Tensor dq, at::Tensor dk, at::Tensor dv, at::Tensor klo, at::Tensor qhi, double scale) {
-  bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, true, scale, fa::Sparse{nullptr, 0, 0}, -1, INT64_MIN,
-           band_of(klo, qhi, q, k));
+  bwd_impl(dout, q, k, v, o, lse, dq, dk, dv, true, scale, kNoSparse, -1, INT64_MIN, band_of(klo, qhi, q, k));
 }
 
 // Causal GQA forward over a ragged token buffer (see fa::Varlen): q [T, Hq, D], k / v [T, Hkv, D], strided
@@ -1429,28 +1326,18 @@ void flash_attn_bwd_band(at::Tensor dout, at::Tensor q, at::Tensor k, at::Tensor
 template <int D>
 static void fwd_varlen_d(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, const at::Tensor& o,
                          const at::Tensor& table, double scale, int window) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds_limit(&fa::fwd_varlen_kernel<D>, 4 * fa::KT * 2 * D);
-    attr = true;
-  }
+  static_assert(kRingBytes<D> <= kMaxDynamicLds, "varlen LDS exceeds the opt-in limit");
   auto st = [](const at::Tensor& t) { return fa::Strides{0, t.stride(0), t.stride(1)}; };
   const int H = q.size(1), N = table.size(0);
-  hipLaunchKernelGGL(fa::fwd_varlen_kernel<D>, dim3(N * H), dim3(fa::NW * 64), 4 * fa::KT * 2 * D, cur_stream(),
-                     reinterpret_cast<const unsigned short*>(q.data_ptr()), st(q),
-                     reinterpret_cast<const unsigned short*>(k.data_ptr()), st(k),
-                     reinterpret_cast<const unsigned short*>(v.data_ptr()), st(v),
-                     reinterpret_cast<unsigned short*>(o.data_ptr()), st(o), H, (int)k.size(1), (float)scale,
-                     fa::Varlen{table.data_ptr<int>(), (int)q.size(0), window});
-  SXE_LAUNCH_CHECK();
+  launch<fa::fwd_varlen_kernel<D>>(N * H, fa::NW, kRingBytes<D>, u16(q), st(q), u16(k), st(k), u16(v), st(v), u16(o),
+                                   st(o), H, (int)k.size(1), (float)scale,
+                                   fa::Varlen{table.data_ptr<int>(), (int)q.size(0), window});
 }
 
 at::Tensor flash_attn_fwd_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor table, double scale,
                                  int64_t window, c10::optional<at::Tensor> out) {
   SXE_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3, "flash_attn varlen: tensors must be [T, H, D]");
   SXE_CHECK(q.is_cuda() && k.device() == q.device() && v.device() == q.device(), "flash_attn varlen: q/k/v on one GPU");
-  SXE_CHECK(q.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kBFloat16 && v.scalar_type() == at::kBFloat16,
-            "flash_attn varlen: bf16 only");
   const int64_t T = q.size(0), H = q.size(1), D = q.size(2);
   SXE_CHECK(D == 64 || D == 128 || D == 256, "flash_attn varlen: head dim must be 64, 128 or 256");
   SXE_CHECK(k.size(2) == D && v.size(2) == D, "flash_attn varlen: q/k/v head dims differ");
@@ -1465,18 +1352,11 @@ at::Tensor flash_attn_fwd_varlen(at::Tensor q, at::Tensor k, at::Tensor v, at::T
   at::Tensor o = out.has_value() && out->defined() ? *out : at::empty({T, H, D}, q.options());
   SXE_CHECK(o.dim() == 3 && o.sizes() == q.sizes() && o.scalar_type() == at::kBFloat16 && o.device() == q.device(),
             "flash_attn varlen: out must be bf16 [T, Hq, D] on the device of q");
-  for (const at::Tensor* t : {&q, &k, &v, &o})
-    SXE_CHECK(t->stride(2) == 1 && (t->stride(0) % 8) == 0 && (t->stride(1) % 8) == 0 &&
-                  (reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0,
-              "flash_attn varlen: unit stride on D and 16-byte aligned rows required");
+  check_bf16_rows({&q, &k, &v, &o}, "flash_attn varlen");
   if (T == 0 || table.size(0) == 0) return o;
   c10::DeviceGuard guard(q.device());
   const int w = window == 0 ? (1 << 30) : (int)std::min<int64_t>(window, 1 << 30);
-  switch (D) {
-    case 64: fwd_varlen_d<64>(q, k, v, o, table, scale, w); break;
-    case 256: fwd_varlen_d<256>(q, k, v, o, table, scale, w); break;
-    default: fwd_varlen_d<128>(q, k, v, o, table, scale, w); break;
-  }
+  dispatch_head_dim(D, "flash_attn varlen", [&](auto d) { fwd_varlen_d<decltype(d)::value>(q, k, v, o, table, scale, w); });
   return o;
 }
 

@@ -615,15 +615,6 @@ __global__ __launch_bounds__(D) void merge_kernel(const float* __restrict__ part
 
 }  // namespace pa
 
-// f(std::integral_constant<int, D>) for a supported head dim
-template <class F>
-static void dispatch_head_dim(int D, const char* op, F&& f) {
-  if (D == 128) f(std::integral_constant<int, 128>{});
-  else if (D == 64) f(std::integral_constant<int, 64>{});
-  else if (D == 256) f(std::integral_constant<int, 256>{});
-  else SXE_CHECK(false, op, ": head_dim must be 64, 128 or 256");
-}
-
 // FP8 cache operands: codes [blocks, 2, nkv, bs, D] e4m3fn, scales [blocks, 2, nkv, bs] fp32, on x's device
 static void check_fp8_cache(const at::Tensor& codes, const at::Tensor& scales, const at::Tensor& x) {
   SXE_CHECK(codes.scalar_type() == at::kFloat8_e4m3fn && codes.dim() == 5 && codes.is_contiguous(),

@@ -160,53 +160,20 @@ def _pad(t, S_pad, D_pad):
     return out
 
 
-def _padded_fwd(q, k, v, causal, scale):
-    Sq, Sk, D = q.shape[1], k.shape[1], q.shape[-1]
-    Dp = _native_dim(D)
-    Sqp, Skp = -(-Sq // TILE) * TILE, -(-Sk // TILE) * TILE
-    qp, kp, vp = _pad(q, Sqp, Dp), _pad(k, Skp, Dp), _pad(v, Skp, Dp)
-    o, lse = torch.ops.sxe.flash_attn_fwd(qp, kp, vp, bool(causal), float(scale), Sk, Sk - Sq)
-    return qp, kp, vp, o, lse
+def _flash_fwd(q, k, v, causal, scale, klo, qhi, *kv_args):
+    """(o, lse) of the flash forward. ``klo`` / ``qhi`` (None = no band) select the band kernels, which
+    are causal by construction; ``kv_args`` = (kv_len, causal_offset) of the padded path."""
+    if klo is not None:
+        return torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
+    return torch.ops.sxe.flash_attn_fwd(q, k, v, bool(causal), float(scale), *kv_args)
 
 
-class _FlashAttnPadded(torch.autograd.Function):
-    """Flash attention on padded copies (see the module docstring)."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        Sq, Sk, D = q.shape[1], k.shape[1], q.shape[-1]
-        qp, kp, vp, o, lse = _padded_fwd(q, k, v, causal, scale)
-        ctx.save_for_backward(qp, kp, vp, o, lse)
-        ctx.meta = (causal, scale, Sq, Sk, D, q.dtype)
-        return o[:, :Sq, :, :D].to(q.dtype)
-
-    @staticmethod
-    def backward(ctx, do):
-        qp, kp, vp, o, lse = ctx.saved_tensors
-        causal, scale, Sq, Sk, D, dtype = ctx.meta
-        dop = _pad(do, qp.shape[1], qp.shape[-1])
-        dq, dk, dv = torch.empty_like(qp), torch.empty_like(kp), torch.empty_like(vp)
-        torch.ops.sxe.flash_attn_bwd(dop, qp, kp, vp, o, lse, dq, dk, dv, bool(causal), float(scale), Sk, Sk - Sq)
-        sq = (slice(None), slice(0, Sq), slice(None), slice(0, D))
-        sk = (slice(None), slice(0, Sk), slice(None), slice(0, D))
-        return dq[sq].to(dtype), dk[sk].to(dtype), dv[sk].to(dtype), None, None
-
-
-class _FlashAttn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
-        o, lse = torch.ops.sxe.flash_attn_fwd(q, k, v, bool(causal), float(scale))
-        ctx.save_for_backward(q, k, v, o, lse)
-        ctx.causal, ctx.scale = causal, scale
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        torch.ops.sxe.flash_attn_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, bool(ctx.causal),
-                                     float(ctx.scale))
-        return dq, dk, dv, None, None
+def _flash_bwd(do, q, k, v, o, lse, dq, dk, dv, causal, scale, klo, qhi, *kv_args):
+    """The flash backward into dq / dk / dv (possibly strided views of one buffer); see ``_flash_fwd``."""
+    if klo is not None:
+        torch.ops.sxe.flash_attn_bwd_band(do, q, k, v, o, lse, dq, dk, dv, klo, qhi, float(scale))
+    else:
+        torch.ops.sxe.flash_attn_bwd(do, q, k, v, o, lse, dq, dk, dv, bool(causal), float(scale), *kv_args)
 
 
 def _pad_bounds(bounds, S_pad):
@@ -222,59 +189,59 @@ def _pad_bounds(bounds, S_pad):
     return kp, qp
 
 
-class _FlashAttnBand(torch.autograd.Function):
+def _padded_kv_args(Sq, Sk, klo):
+    # a band needs no kv_len: its pad tokens are one trailing document, so no real query sees a pad key
+    return (Sk, Sk - Sq) if klo is None else ()
+
+
+def _padded_fwd(q, k, v, causal, scale, klo=None, qhi=None):
+    Sq, Sk, D = q.shape[1], k.shape[1], q.shape[-1]
+    Dp = _native_dim(D)
+    Sqp, Skp = -(-Sq // TILE) * TILE, -(-Sk // TILE) * TILE
+    qp, kp, vp = _pad(q, Sqp, Dp), _pad(k, Skp, Dp), _pad(v, Skp, Dp)
+    if klo is not None:
+        klo, qhi = _pad_bounds((klo, qhi), Sqp)
+    o, lse = _flash_fwd(qp, kp, vp, causal, scale, klo, qhi, *_padded_kv_args(Sq, Sk, klo))
+    return qp, kp, vp, o, lse, klo, qhi
+
+
+class _FlashAttnPadded(torch.autograd.Function):
+    """Flash attention on padded copies (see the module docstring)."""
+
     @staticmethod
-    def forward(ctx, q, k, v, klo, qhi, scale):
-        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
+    def forward(ctx, q, k, v, causal, scale, klo, qhi):
+        Sq, Sk, D = q.shape[1], k.shape[1], q.shape[-1]
+        qp, kp, vp, o, lse, klo, qhi = _padded_fwd(q, k, v, causal, scale, klo, qhi)
+        ctx.save_for_backward(qp, kp, vp, o, lse, klo, qhi)
+        ctx.meta = (causal, scale, Sq, Sk, D, q.dtype)
+        return o[:, :Sq, :, :D].to(q.dtype)
+
+    @staticmethod
+    def backward(ctx, do):
+        qp, kp, vp, o, lse, klo, qhi = ctx.saved_tensors
+        causal, scale, Sq, Sk, D, dtype = ctx.meta
+        dop = _pad(do, qp.shape[1], qp.shape[-1])
+        dq, dk, dv = torch.empty_like(qp), torch.empty_like(kp), torch.empty_like(vp)
+        _flash_bwd(dop, qp, kp, vp, o, lse, dq, dk, dv, causal, scale, klo, qhi, *_padded_kv_args(Sq, Sk, klo))
+        sq = (slice(None), slice(0, Sq), slice(None), slice(0, D))
+        sk = (slice(None), slice(0, Sk), slice(None), slice(0, D))
+        return dq[sq].to(dtype), dk[sk].to(dtype), dv[sk].to(dtype), None, None, None, None
+
+
+class _FlashAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, klo, qhi):
+        o, lse = _flash_fwd(q, k, v, causal, scale, klo, qhi)
         ctx.save_for_backward(q, k, v, o, lse, klo, qhi)
-        ctx.scale = scale
+        ctx.causal, ctx.scale = causal, scale
         return o
 
     @staticmethod
     def backward(ctx, do):
         q, k, v, o, lse, klo, qhi = ctx.saved_tensors
         dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(ctx.scale))
-        return dq, dk, dv, None, None, None
-
-
-class _FlashAttnBandPadded(torch.autograd.Function):
-    """Band attention on padded copies: the pad tokens are one trailing document, so no real query
-    sees a pad key and the kernels' ``kv_len`` is not needed."""
-
-    @staticmethod
-    def forward(ctx, q, k, v, klo, qhi, scale):
-        S, D = q.shape[1], q.shape[-1]
-        Dp, Sp = _native_dim(D), -(-S // TILE) * TILE
-        qp, kp, vp = _pad(q, Sp, Dp), _pad(k, Sp, Dp), _pad(v, Sp, Dp)
-        klo, qhi = _pad_bounds((klo, qhi), Sp)
-        o, lse = torch.ops.sxe.flash_attn_fwd_band(qp, kp, vp, klo, qhi, float(scale))
-        ctx.save_for_backward(qp, kp, vp, o, lse, klo, qhi)
-        ctx.meta = (scale, S, D, q.dtype)
-        return o[:, :S, :, :D].to(q.dtype)
-
-    @staticmethod
-    def backward(ctx, do):
-        qp, kp, vp, o, lse, klo, qhi = ctx.saved_tensors
-        scale, S, D, dtype = ctx.meta
-        dop = _pad(do, qp.shape[1], qp.shape[-1])
-        dq, dk, dv = torch.empty_like(qp), torch.empty_like(kp), torch.empty_like(vp)
-        torch.ops.sxe.flash_attn_bwd_band(dop, qp, kp, vp, o, lse, dq, dk, dv, klo, qhi, float(scale))
-        sl = (slice(None), slice(0, S), slice(None), slice(0, D))
-        return dq[sl].to(dtype), dk[sl].to(dtype), dv[sl].to(dtype), None, None, None
-
-
-def _attention_band(q, k, v, causal, scale, bounds):
-    _check_band(q, k, causal, bounds)
-    if q.is_cuda:
-        native.require_hip()
-        if hip_supported(q, k, v):
-            return _FlashAttnBand.apply(q, k, v, bounds[0], bounds[1], scale)
-        if hip_paddable(q, k, v):
-            return _FlashAttnBandPadded.apply(q, k, v, bounds[0], bounds[1], scale)
-        warning_once(f"sxe attention: HIP flash kernel does not cover dtype={q.dtype} D={q.shape[-1]} "
-                     f"S={q.shape[1]}; using SDPA")
-    return _sdpa(q, k, v, True, scale, band_mask(bounds, q.shape[1]))
+        _flash_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, ctx.causal, ctx.scale, klo, qhi)
+        return dq, dk, dv, None, None, None, None
 
 
 def attention(q, k, v, causal=True, softmax_scale=None, bounds=None):
@@ -282,72 +249,47 @@ def attention(q, k, v, causal=True, softmax_scale=None, bounds=None):
     and ``causal`` the mask is bottom-right aligned (query i sees keys <= i + Sk - Sq). ``bounds``
     (from ``band_bounds``; needs causal and Sq == Sk) narrows the mask to packed documents / a window."""
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    klo, qhi = None, None
     if bounds is not None:
-        return _attention_band(q, k, v, causal, scale, bounds)
+        _check_band(q, k, causal, bounds)
+        klo, qhi = bounds
     if q.is_cuda:
         native.require_hip()
         if hip_supported(q, k, v):
-            return _FlashAttn.apply(q, k, v, causal, scale)
+            return _FlashAttn.apply(q, k, v, causal, scale, klo, qhi)
         if hip_paddable(q, k, v):
-            return _FlashAttnPadded.apply(q, k, v, causal, scale)
+            return _FlashAttnPadded.apply(q, k, v, causal, scale, klo, qhi)
         warning_once(f"sxe attention: HIP flash kernel does not cover dtype={q.dtype} D={q.shape[-1]} "
                      f"S={q.shape[1]}; using SDPA")
-    return _sdpa(q, k, v, causal, scale)
+    return _sdpa(q, k, v, causal, scale, band_mask(bounds, q.shape[1]) if bounds is not None else None)
 
 
 class _FlashAttnQKVRope(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, cos, sin, nq, nkv, causal, scale, pos):
+    def forward(ctx, qkv, cos, sin, nq, nkv, causal, scale, pos, klo, qhi):
         B, S = qkv.shape[0], qkv.shape[1]
         if cos is not None:
             torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
         q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        o, lse = torch.ops.sxe.flash_attn_fwd(q, k, v, bool(causal), float(scale))
+        o, lse = _flash_fwd(q, k, v, causal, scale, klo, qhi)
         # qkv (the fresh QKV-projection output, consumed only here) was rotated in place; it is
         # saved AFTER the rotation, and no other autograd node holds it, so it is not marked dirty
         # (a dirty view input would forbid returning it).
-        ctx.save_for_backward(qkv, o, lse, cos, sin, pos)
+        ctx.save_for_backward(qkv, o, lse, cos, sin, pos, klo, qhi)
         ctx.meta = (nq, nkv, causal, scale)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        qkv, o, lse, cos, sin, pos = ctx.saved_tensors
+        qkv, o, lse, cos, sin, pos, klo, qhi = ctx.saved_tensors
         nq, nkv, causal, scale = ctx.meta
         dqkv = torch.empty_like(qkv)
         q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
         dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
-        torch.ops.sxe.flash_attn_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, bool(causal), float(scale))
+        _flash_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, causal, scale, klo, qhi)
         if cos is not None:
             torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, qkv.shape[1], 0, True)
-        return dqkv, None, None, None, None, None, None, None
-
-
-class _FlashAttnQKVRopeBand(torch.autograd.Function):
-    """``_FlashAttnQKVRope`` with a band mask (causal)."""
-
-    @staticmethod
-    def forward(ctx, qkv, cos, sin, nq, nkv, scale, pos, klo, qhi):
-        S = qkv.shape[1]
-        if cos is not None:
-            torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
-        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
-        ctx.save_for_backward(qkv, o, lse, cos, sin, pos, klo, qhi)  # see _FlashAttnQKVRope on qkv
-        ctx.meta = (nq, nkv, scale)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        qkv, o, lse, cos, sin, pos, klo, qhi = ctx.saved_tensors
-        nq, nkv, scale = ctx.meta
-        dqkv = torch.empty_like(qkv)
-        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
-        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(scale))
-        if cos is not None:
-            torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, qkv.shape[1], 0, True)
-        return dqkv, None, None, None, None, None, None, None, None
+        return dqkv, None, None, None, None, None, None, None, None, None
 
 
 def attention_qkv_rope(qkv, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None, bounds=None):
@@ -362,10 +304,11 @@ def attention_qkv_rope(qkv, nq, nkv, rope=None, position_ids=None, causal=True, 
             pos = position_ids.reshape(-1).contiguous().long() if position_ids is not None else None
             cos = rope.cos if rope is not None else None
             sin = rope.sin if rope is not None else None
+            klo, qhi = None, None
             if bounds is not None:
                 _check_band(q, k, causal, bounds)
-                return _FlashAttnQKVRopeBand.apply(qkv, cos, sin, nq, nkv, scale, pos, bounds[0], bounds[1])
-            return _FlashAttnQKVRope.apply(qkv, cos, sin, nq, nkv, causal, scale, pos)
+                klo, qhi = bounds
+            return _FlashAttnQKVRope.apply(qkv, cos, sin, nq, nkv, causal, scale, pos, klo, qhi)
     if rope is not None:
         from .rope import apply_rope_qkv_
         qkv = apply_rope_qkv_(qkv, rope, nq + nkv, position_ids)
@@ -383,27 +326,27 @@ class _QKVProjAttn(torch.autograd.Function):
     NT one (0.84 ms); the two transposes cost ~0.13 ms (profiles/r06/wgrad_variants_16k.log)."""
 
     @staticmethod
-    def forward(ctx, x, w, cos, sin, nq, nkv, causal, scale, pos):
+    def forward(ctx, x, w, cos, sin, nq, nkv, causal, scale, pos, klo, qhi):
         B, S, H = x.shape
         x2 = x.reshape(-1, H)
         qkv = F.linear(x2, w).view(B, S, nq + 2 * nkv, -1)
         if cos is not None:
             torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
         q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        o, lse = torch.ops.sxe.flash_attn_fwd(q, k, v, bool(causal), float(scale))
+        o, lse = _flash_fwd(q, k, v, causal, scale, klo, qhi)
         xT = torch.ops.sxe.transpose16(x2) if ctx.needs_input_grad[1] else None
-        ctx.save_for_backward(xT, qkv, o, lse, cos, sin, pos, w)
+        ctx.save_for_backward(xT, qkv, o, lse, cos, sin, pos, w, klo, qhi)
         ctx.meta = (nq, nkv, causal, scale, x.shape)
         return o
 
     @staticmethod
     def backward(ctx, do):
-        xT, qkv, o, lse, cos, sin, pos, w = ctx.saved_tensors
+        xT, qkv, o, lse, cos, sin, pos, w, klo, qhi = ctx.saved_tensors
         nq, nkv, causal, scale, x_shape = ctx.meta
         dqkv = torch.empty_like(qkv)
         q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
         dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
-        torch.ops.sxe.flash_attn_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, bool(causal), float(scale))
+        _flash_bwd(do.contiguous(), q, k, v, o, lse, dq, dk, dv, causal, scale, klo, qhi)
         del q, k, v, o, lse, qkv
         if cos is not None:
             torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, dqkv.shape[1], 0, True)
@@ -414,45 +357,7 @@ class _QKVProjAttn(torch.autograd.Function):
         dw = None
         if ctx.needs_input_grad[1]:
             dw = weight_grad_tn(w, torch.ops.sxe.transpose16(d2), xT, fp32_out=True)
-        return dx, dw, None, None, None, None, None, None, None
-
-
-class _QKVProjAttnBand(torch.autograd.Function):
-    """``_QKVProjAttn`` with a band mask (causal)."""
-
-    @staticmethod
-    def forward(ctx, x, w, cos, sin, nq, nkv, scale, pos, klo, qhi):
-        B, S, H = x.shape
-        x2 = x.reshape(-1, H)
-        qkv = F.linear(x2, w).view(B, S, nq + 2 * nkv, -1)
-        if cos is not None:
-            torch.ops.sxe.rope_(qkv[:, :, :nq + nkv], cos, sin, pos, S, 0, False)
-        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        o, lse = torch.ops.sxe.flash_attn_fwd_band(q, k, v, klo, qhi, float(scale))
-        xT = torch.ops.sxe.transpose16(x2) if ctx.needs_input_grad[1] else None
-        ctx.save_for_backward(xT, qkv, o, lse, cos, sin, pos, w, klo, qhi)
-        ctx.meta = (nq, nkv, scale, x.shape)
-        return o
-
-    @staticmethod
-    def backward(ctx, do):
-        xT, qkv, o, lse, cos, sin, pos, w, klo, qhi = ctx.saved_tensors
-        nq, nkv, scale, x_shape = ctx.meta
-        dqkv = torch.empty_like(qkv)
-        q, k, v = qkv[:, :, :nq], qkv[:, :, nq:nq + nkv], qkv[:, :, nq + nkv:]
-        dq, dk, dv = dqkv[:, :, :nq], dqkv[:, :, nq:nq + nkv], dqkv[:, :, nq + nkv:]
-        torch.ops.sxe.flash_attn_bwd_band(do.contiguous(), q, k, v, o, lse, dq, dk, dv, klo, qhi, float(scale))
-        del q, k, v, o, lse, qkv
-        if cos is not None:
-            torch.ops.sxe.rope_(dqkv[:, :, :nq + nkv], cos, sin, pos, dqkv.shape[1], 0, True)
-        d2 = dqkv.view(-1, w.shape[0])
-        from .linear import data_grad
-        from .mlp import weight_grad_tn
-        dx = data_grad(d2, w).view(x_shape) if ctx.needs_input_grad[0] else None
-        dw = None
-        if ctx.needs_input_grad[1]:
-            dw = weight_grad_tn(w, torch.ops.sxe.transpose16(d2), xT, fp32_out=True)
-        return dx, dw, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None
 
 
 def qkv_proj_attention(x, qkv_proj, nq, nkv, rope=None, position_ids=None, causal=True, softmax_scale=None,
@@ -474,11 +379,12 @@ def qkv_proj_attention(x, qkv_proj, nq, nkv, rope=None, position_ids=None, causa
             pos = position_ids.reshape(-1).contiguous().long() if position_ids is not None else None
             cos = rope.cos if rope is not None else None
             sin = rope.sin if rope is not None else None
+            klo, qhi = None, None
             if bounds is not None:
-                if not causal or tuple(bounds[0].shape) != (B, S) or tuple(bounds[1].shape) != (B, S):
+                klo, qhi = bounds
+                if not causal or tuple(klo.shape) != (B, S) or tuple(qhi.shape) != (B, S):
                     raise ValueError("attention bounds need causal=True and [B, S] tensors")
-                return _QKVProjAttnBand.apply(x, w, cos, sin, nq, nkv, scale, pos, bounds[0], bounds[1])
-            return _QKVProjAttn.apply(x, w, cos, sin, nq, nkv, causal, scale, pos)
+            return _QKVProjAttn.apply(x, w, cos, sin, nq, nkv, causal, scale, pos, klo, qhi)
     qkv = qkv_proj(x).view(B, S, N, -1)
     return attention_qkv_rope(qkv, nq, nkv, rope, position_ids, causal, softmax_scale, bounds)
 
@@ -490,7 +396,7 @@ def attention_with_lse(q, k, v, causal=True, softmax_scale=None):
         return torch.ops.sxe.flash_attn_fwd(q, k, v, bool(causal), float(scale))
     if q.is_cuda and hip_paddable(q, k, v):
         Sq, D = q.shape[1], q.shape[-1]
-        _, _, _, o, lse = _padded_fwd(q, k, v, causal, scale)
+        o, lse = _padded_fwd(q, k, v, causal, scale)[3:5]
         return o[:, :Sq, :, :D].to(q.dtype), lse[:, :, :Sq].contiguous()
     return reference_attention(q, k, v, causal, scale, return_lse=True)
 

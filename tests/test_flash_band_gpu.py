@@ -85,6 +85,19 @@ def test_band_long_document_wave_variants(waves, monkeypatch):
     _check(q, k, v, _bounds(512, [[0, 300]]))
 
 
+@pytest.mark.parametrize("D,fwd_waves,dma,bwd_waves", [(128, 4, "1", 4), (64, 4, "0", 8), (128, 8, "0", 8)])
+def test_band_forward_knobs(D, fwd_waves, dma, bwd_waves, monkeypatch):
+    """The forward knobs in band mode at a length that allows 8 waves: SXE_FA_FWD_WAVES=4 narrows the
+    band forward too, SXE_FA_FWD_DMA=0 is ignored by it (the band forward is always the LDS-DMA one);
+    head dim 64 with the 8-wave band dQ."""
+    monkeypatch.setenv("SXE_FA_FWD_WAVES", str(fwd_waves))
+    monkeypatch.setenv("SXE_FA_FWD_DMA", dma)
+    monkeypatch.setenv("SXE_FA_DQ_WAVES", str(bwd_waves))
+    monkeypatch.setenv("SXE_FA_DKDV_WAVES", str(bwd_waves))
+    q, k, v = _qkv(1, 256, 2, 1, D)
+    _check(q, k, v, _bounds(256, [[0, 100]]))
+
+
 @pytest.mark.parametrize("hpw", [1, 2, 4])
 def test_band_dkdv_heads_per_workgroup(hpw, monkeypatch):
     monkeypatch.setenv("SXE_FA_DKDV_HPW", str(hpw))
@@ -188,13 +201,14 @@ def test_band_qkv_proj_attention_fused():
     x = torch.randn(B, S, Hd, device="cuda", dtype=torch.bfloat16, requires_grad=True)
     bounds = _bounds(S, STARTS_384)
     ran = []
-    orig = att._QKVProjAttnBand.apply
-    att._QKVProjAttnBand.apply = lambda *a: (ran.append(1), orig(*a))[1]
+    orig = att._QKVProjAttn.apply
+    att._QKVProjAttn.apply = lambda *a: (ran.append(a[-2:]), orig(*a))[1]  # (klo, qhi) trail the arguments
     try:
         o = att.qkv_proj_attention(x, proj, nq, nkv, None, None, causal=True, bounds=bounds)
     finally:
-        att._QKVProjAttnBand.apply = orig
-    assert ran, "the fused QKV-projection band node did not run"
+        att._QKVProjAttn.apply = orig
+    assert len(ran) == 1, "the fused QKV-projection node did not run"
+    assert ran[0][0] is bounds[0] and ran[0][1] is bounds[1], "the fused node did not get the band bounds"
     do = torch.randn(B, S, nq, D, device="cuda")
     (o.float() * do).sum().backward()
     qkv = torch.nn.functional.linear(x.detach(), proj.weight.detach()).view(B, S, nq + 2 * nkv, D)
@@ -252,14 +266,16 @@ def test_llama_packed_samples_gpu():
     pos = _pos(S, [[0, cut], [0, cut]], "cpu")
     lr = ref(ids, labels=ids, position_ids=pos)
     ran = []
-    orig = att._QKVProjAttnBand.apply
-    att._QKVProjAttnBand.apply = lambda *a: (ran.append(1), orig(*a))[1]
+    orig = att._QKVProjAttn.apply
+    att._QKVProjAttn.apply = lambda *a: (ran.append(a[-2:]), orig(*a))[1]  # (klo, qhi) trail the arguments
     try:
         ld = dev(ids.cuda(), labels=ids.cuda(), position_ids=pos.cuda())
         ld.backward()
     finally:
-        att._QKVProjAttnBand.apply = orig
-    assert len(ran) == 2, "both layers must run the band kernels"
+        att._QKVProjAttn.apply = orig
+    assert len(ran) == 2, "both layers must run the fused node"
+    assert all(torch.is_tensor(klo) and torch.is_tensor(qhi) for klo, qhi in ran), \
+        "both layers must run the band kernels"
     print("loss gpu / cpu:", float(ld), float(lr))
     assert abs(float(ld) - float(lr)) / float(lr) < 2e-2
     assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in dev.parameters())

@@ -63,11 +63,26 @@ def _rel(a, b):
     ("longformer64_uni", True, 4, 96), ("local128", False, 2, 256)])
 def test_block_sparse_flash_matches_reference(cfg, causal, hk, D, monkeypatch):
     """Every head dim runs the flash kernels (BERT's 64 included): the reference path must not run."""
+    _sparse_flash_case(cfg, causal, 2, 4, hk, 512, D, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fwd_waves,dma,bwd_waves", [("4", "0", "8"), ("4", "1", "8"), ("8", "0", "4")])
+def test_block_sparse_flash_kernel_variants(fwd_waves, dma, bwd_waves, monkeypatch):
+    """The sparse forms of the kernel variants the defaults do not pick at this length: 4-wave and
+    register-staged forwards, 8-wave dQ and dK/dV."""
+    monkeypatch.setenv("SXE_FA_FWD_WAVES", fwd_waves)
+    monkeypatch.setenv("SXE_FA_FWD_DMA", dma)
+    monkeypatch.setenv("SXE_FA_DQ_WAVES", bwd_waves)
+    monkeypatch.setenv("SXE_FA_DKDV_WAVES", bwd_waves)
+    _sparse_flash_case("longformer64_uni", True, 1, 2, 1, 256, 128, monkeypatch)
+
+
+def _sparse_flash_case(cfg, causal, B, H, hk, S, D, monkeypatch):
     from shuffle_exchange_amd.ops import native
     from shuffle_exchange_amd.ops import sparse_attention as sa
     native.require_hip()
     torch.manual_seed(0)
-    B, H, S = 2, 4, 512
     monkeypatch.setattr(sa, "sparse_attention_reference", None)
     ref_fn = _REF
     conf = {"fixed16": lambda: sa.FixedSparsityConfig(H, block=16, num_local_blocks=4, different_layout_per_head=True,

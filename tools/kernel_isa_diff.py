@@ -6,13 +6,18 @@ Only lines containing `__hip_cuid_` (the per-compilation-unit id) are dropped be
 are the one thing that differs when nothing changed. Prints `identical` or the first differing
 lines per file and exits non-zero on any difference.
 
-Usage: python tools/kernel_isa_diff.py <git-ref> [-j N] [file.hip ...]
+With --by-symbol a file whose text differs is compared function by function instead (same set of
+symbols, identical text and metadata per symbol): a host-side change can make the compiler emit the
+same kernels in another order.
+
+Usage: python tools/kernel_isa_diff.py [-j N] [--by-symbol] <git-ref> [file.hip ...]
 """
 import argparse
 import concurrent.futures as cf
 import difflib
 import io
 import os
+import re
 import subprocess
 import sys
 import tarfile
@@ -33,6 +38,53 @@ def _asm(csrc, name, out):
         return [ln for ln in f if "__hip_cuid_" not in ln]
 
 
+_BLOCK = re.compile(r"(?<![A-Za-z0-9_])((?:\.L)?BB)\d+_(\d+)")  # also named in comments: `Header=BB12_3`
+_LABEL = re.compile(r"\.L([A-Za-z_]+?)(\d+)(_\d+)?\b")
+
+
+def _by_symbol(lines):
+    """{symbol: lines} of one assembly file, for comparing two files that hold the same functions in
+    a different order: a function's text from its `Begin function` line to the end of its `Kernel
+    info` comment, then its entry of the metadata. Everything else is kept under "". Local labels carry
+    the function's index in the file (`.LBB12_3`, `.Lfunc_end12`): the index is dropped, and counters
+    that run through the whole file (`.Ltmp7`) are renumbered from 0 per function."""
+    out = {"": []}
+    cur, ended, meta, entry = "", False, False, []
+
+    def file_entry():  # a list item of the metadata goes to the kernel its `.name` gives
+        names = [x.split(":", 1)[1].strip() for x in entry if x.startswith("    .name:")]
+        out.setdefault(names[0] if names else "", []).extend(entry)
+        entry.clear()
+    for ln in lines:
+        if ln.startswith("\t.amdgpu_metadata"):
+            cur, meta = "", True
+        if meta:
+            if ln.startswith("  - ") or not ln.startswith("  "):
+                file_entry()
+            entry.append(ln)
+            continue
+        if "; -- Begin function " in ln:
+            head = [out[cur].pop()] if out[cur] and out[cur][-1].startswith("\t.section\t.text") else []
+            cur, ended = ln.rsplit(" ", 1)[1].strip(), False
+            out[cur] = head
+        elif "; -- End function" in ln:
+            ended = True
+        elif ended and not (ln.startswith("\t.set " + cur + ".") or ln.startswith(";") or ".AMDGPU.csdata" in ln):
+            cur, ended = "", False
+        out[cur].append(ln)
+    file_entry()
+    for sym, body in out.items():
+        seen = {}
+
+        def norm(m):
+            if m.group(3) or m.group(1).startswith("func_"):  # per-function index: .LBB12_3 -> .LBB_3
+                return ".L" + m.group(1) + (m.group(3) or "")
+            return ".L" + m.group(1) + str(seen.setdefault(m.group(0), len(seen)))
+        # (the comment column moves with the label's width)
+        out[sym] = [re.sub(r"[ \t]+;", " ;", _LABEL.sub(norm, _BLOCK.sub(r"\1_\2", ln))) for ln in body]
+    return out
+
+
 def _kernels(csrc):
     return {f for f in os.listdir(os.path.join(csrc, "kernels")) if f.endswith(".hip")}
 
@@ -43,6 +95,9 @@ def main():
     ap.add_argument("files", nargs="*", help="kernel file names (default: all)")
     ap.add_argument("-j", "--jobs", type=int, default=8)
     ap.add_argument("--context", type=int, default=20, help="diff lines shown per file")
+    ap.add_argument("--by-symbol", action="store_true",
+                    help="a file whose text differs: compare per function symbol (same set, same text and "
+                         "metadata each), for a host change that only reorders the emitted functions")
     a = ap.parse_args()
 
     with tempfile.TemporaryDirectory(prefix="sxe-isa-") as tmp:
@@ -67,6 +122,18 @@ def main():
                 old, new = futs[n, "ref"].result(), futs[n, "new"].result()
                 if old == new:
                     print(f"{n}: identical ({len(new)} lines)", flush=True)
+                    continue
+                if a.by_symbol:
+                    so, sn = _by_symbol(old), _by_symbol(new)
+                    diff = sorted(s for s in set(so) | set(sn) if so.get(s) != sn.get(s))
+                    if not diff:
+                        print(f"{n}: identical per symbol ({len(sn) - 1} symbols, in another order)", flush=True)
+                        continue
+                    bad += 1
+                    print(f"{n}: {len(diff)} of {len(set(so) | set(sn)) - 1} symbols DIFFER", flush=True)
+                    for s in diff:
+                        where = "differs" if s in so and s in sn else ("only in " + (a.ref if s in so else "working tree"))
+                        print(f"  {s or '(outside any function)'}: {where}")
                     continue
                 bad += 1
                 print(f"{n}: DIFFERS", flush=True)
