@@ -54,6 +54,9 @@ __device__ __forceinline__ int fp6_index(float a) {
 // ------------------------------------------------------------ group quantize / dequantize
 // One wave per group: amax -> scale = amax / fmax (1 if the group is zero), then codes. FP4 writes
 // two codes per byte (element 2j in the low nibble), FP6 one code per byte (FP_Quantize layout).
+// NaN or +-Inf in a group gives a non-finite scale (same policy as quant.hip): its codes are in
+// range and every element dequantizes to a non-finite value. The codes divide (x / s), so an exact
+// zero always has magnitude code 0.
 template <int BITS, DT T>
 __global__ void __launch_bounds__(256) quant_kernel(const typename dt_traits<T>::storage* __restrict__ x,
                                                     uint8_t* __restrict__ q, float* __restrict__ scales,
@@ -62,11 +65,12 @@ __global__ void __launch_bounds__(256) quant_kernel(const typename dt_traits<T>:
   constexpr float FMAX = BITS == 4 ? 6.f : 28.f;
   for (int64_t gi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); gi < groups; gi += (int64_t)gridDim.x * 4) {
     const auto* xg = x + gi * gsize;
-    float amax = 0.f;
-    for (int j = lane; j < gsize; j += 64) amax = fmaxf(amax, fabsf(to_f32<T>(xg[j])));
+    int mb = 0;  // |x| bit patterns order like the values and NaN sorts above Inf: a max that keeps NaN
+    for (int j = lane; j < gsize; j += 64) mb = max(mb, (int)(__float_as_uint(to_f32<T>(xg[j])) & 0x7fffffffu));
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    const float s = amax > 0.f ? amax / FMAX : 1.f;
+    for (int off = 32; off > 0; off >>= 1) mb = max(mb, __shfl_xor(mb, off, 64));
+    float s = __uint_as_float((unsigned)mb) / FMAX;
+    if (s == 0.f) s = 1.f;  // zero group, or amax / FMAX underflows; a NaN / Inf scale stays as it is
     if (lane == 0) scales[gi] = s;
     if constexpr (BITS == 4) {
       uint8_t* qg = q + gi * (gsize / 2);

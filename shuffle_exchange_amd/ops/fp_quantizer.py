@@ -35,7 +35,7 @@ import math
 import torch
 
 from . import native
-from .quantizer import dequantize_fp8, quantize_fp8
+from .quantizer import _group_scale, dequantize_fp8, quantize_fp8
 
 _FMT = {8: (4, 3), 6: (3, 2), 4: (2, 1)}  # q_bits -> (exponent bits, mantissa bits)
 
@@ -96,10 +96,8 @@ class FP_Quantize:
             q, s = torch.ops.sxe.fpx_quantize(x, q_bits, self.group_size)
         else:
             g = x.float().reshape(-1, self.group_size)
-            amax = g.abs().amax(1)
-            fmax = float(_TABLES[q_bits][-1])
-            s = torch.where(amax > 0, amax / fmax, torch.ones_like(amax))
-            codes = _encode(g / s[:, None], q_bits).reshape(-1).to(torch.uint8)
+            s = _group_scale(g, float(_TABLES[q_bits][-1]))  # NaN / Inf -> non-finite scale, as mxfp.hip
+            codes = _encode(torch.nan_to_num(g / s[:, None], nan=0.0), q_bits).reshape(-1).to(torch.uint8)
             q = (codes[0::2] | (codes[1::2] << 4)) if q_bits == 4 else codes
         self.scale = s
         return (q, s) if return_meta_tensor else q

@@ -9,12 +9,19 @@ import torch
 from . import native
 
 
+def _group_scale(xf, qmax):
+    """Scale policy of quant.hip: amax / qmax; NaN or Inf in a group gives a non-finite scale (amax
+    propagates NaN); a zero quotient (zero group, fp32 underflow) becomes 1."""
+    s = xf.abs().amax(1) / qmax
+    return torch.where(s == 0, torch.ones_like(s), s)
+
+
 def _ref_quant(x, group, bits):
     xf = x.float().reshape(-1, group)
     qmax = 127.0 if bits == 8 else 7.0
-    m = xf.abs().amax(1)
-    s = torch.where(m > 0, m / qmax, torch.ones_like(m))
-    q = torch.clamp(torch.round(xf / s[:, None]), -qmax, qmax).to(torch.int32).reshape(-1)
+    s = _group_scale(xf, qmax)
+    t = torch.clamp(torch.round(xf / s[:, None]), -qmax, qmax)
+    q = torch.where(torch.isnan(t), torch.full_like(t, qmax), t).to(torch.int32).reshape(-1)  # codes stay in range
     if bits == 8:
         return q.to(torch.int8).view(torch.uint8), s
     lo, hi = q[0::2] & 0xF, q[1::2] & 0xF
@@ -85,10 +92,10 @@ def quantize_fp8(x, group_size=128):
         q, s = torch.ops.sxe.quantize_fp8(x, int(group_size))
         return q, s
     xf = x.float().reshape(-1, group_size)
-    m = xf.abs().amax(1)
-    s = torch.where(m > 0, m / 448.0, torch.ones_like(m))
-    q = (xf / s[:, None]).clamp(-448, 448).to(torch.float8_e4m3fn).view(torch.uint8).reshape(-1)
-    return q, s
+    s = _group_scale(xf, 448.0)
+    t = (xf / s[:, None]).clamp(-448, 448)
+    t = torch.where(torch.isnan(t), torch.full_like(t, 448.0), t)  # no NaN code: the scale carries it
+    return t.to(torch.float8_e4m3fn).view(torch.uint8).reshape(-1), s
 
 
 def dequantize_fp8(q, scales, group_size=128, out=None, dtype=torch.bfloat16):
